@@ -12,7 +12,13 @@ problem (BASELINE.json configs[2]; SURVEY.md section 8d "C3").
 Untimed preamble per rank (reported in the JSON): synthetic K(rho), fundamental path u = K^-1 f,
 G(u), shift selection, factorisation of K + sigma G, the IRAM eigensolve.
 
-  python bench.py [--gpus G] [--steps 10] [--warmup 2]
+A plain run sets up, warms up, times the steps and prints the headline line.  --full adds everything else the line
+has carried: the repeated eigensolve and design-point figures, the numpy-surface, Arnoldi-form and extra = 0 legs, the
+scaling models (C3 and C5), the residual and finite-difference checks, the kernel rooflines, the device assembly and
+the CPU baseline.  --dump-outputs DIR saves what the last timed step returned (psi on a fixed sample of rows, df/dx,
+the coefficients of the repeated pairs, if any) as .npy files.
+
+  python bench.py [--gpus G] [--steps 10] [--warmup 2] [--full] [--dump-outputs DIR]
       G > 1 without a launcher: this process starts G rank processes itself (before it touches the GPU; it never
       does) and relays rank 0's JSON line.
   python -m torch.distributed.run --nproc-per-node G ... bench.py --gpus G ...
@@ -200,6 +206,28 @@ def measured_mfma(entry, sources, useful_flops, us_per_launch):
                     "really issued need pipe_time_us; the launch takes us_per_launch"}
 
 
+DUMP_PSI_ROWS = 65536
+
+
+def dump_outputs(dirname, dpsi, data, dfdx):
+    """
+    What a caller of the timed step receives, as float64 .npy files under ``dirname``: psi (n x N, too large to keep
+    whole) on DUMP_PSI_ROWS rows drawn by default_rng(0) -- the same rows for the same problem size -- and their
+    indices, df/dx, and the coefficients of the repeated pairs as rows (i, j, xi, eta) -- only when the step found
+    repeated pairs (none at C3): no empty array is written.
+    """
+    os.makedirs(dirname, exist_ok=True)
+    psi = dpsi.get() if hasattr(dpsi, "get") else np.asarray(dpsi)
+    n = psi.shape[0]
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_PSI_ROWS), replace=False))
+    out = {"psi_sample": psi[rows], "psi_sample_rows": rows, "dfdx": np.asarray(dfdx)}
+    corr = [(i, j, xi, eta) for i, lst in sorted(data.items()) for j, xi, eta in lst] if data else []
+    if corr:
+        out["adj_corr_data"] = np.array(corr, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 class _LastOfMany:
     """stand-in communicator of the LAST rank of P (it owns the slowest mode): no collective, partial results"""
 
@@ -309,7 +337,8 @@ def main_c5(args):
     """
     Config C5 (stand-in for the reference's CRM wingbox, examples/crm.py): thin-walled shell box, 6 dof per
     node, ~2.0 M dof, 64 modes, IRAM m = 129; step = solve_adjoint (sibk, rtol 1e-10, 80 Krylov vectors) +
-    add_total_derivative w.r.t. the wall-thickness groups, operands resident in HBM.  One GPU.
+    add_total_derivative w.r.t. the wall-thickness groups, operands resident in HBM.  One GPU.  A configuration run on
+    request only: its residual, sweep roofline and scaling model are part of its line with or without --full.
     """
     box, dev, ctx, solver, sigma, fstats, Phib, dPhib, step, (t_setup, t_eig), (N, m) = c5_setup(args)
     rng = np.random.default_rng(2)
@@ -322,6 +351,8 @@ def main_c5(args):
         dpsi, data, dfdx = step()
     ctx.sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dpsi, data, dfdx)
     res, _ = solver.eval_adjoint_residual_norm(dPhib, dpsi, b_ortho=True)
     Xs, Xo = ctx.from_host(rng.normal(size=(box.n, 32))), ctx.empty(box.n, 32)
     for _ in range(2):
@@ -392,6 +423,13 @@ def main():
     ap.add_argument("--no-extras0-leg", action="store_true", help="skip the untimed step without extra deflated pairs")
     ap.add_argument("--no-c5-scaling-model", action="store_true", help="skip the scaling model of config C5 (64 modes)")
     ap.add_argument("--dump-dfdx", default=None, help="rank 0 saves the df/dx of the last timed step to this .npy file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step returned to DIR/<name>.npy (float64): psi on a fixed, "
+                         "seeded sample of rows, df/dx and, if the step found any, the coefficients of the repeated pairs")
+    ap.add_argument("--full", action="store_true",
+                    help="C3: everything besides the headline: repeated eigensolve, numpy-surface, Arnoldi-form and extra = 0 "
+                         "legs, scaling models, accuracy and finite-difference checks, rooflines, device assembly, CPU "
+                         "baseline (the --no-* / --cpu-* / --numpy-steps / --spmv-reps options shape these legs)")
     ap.add_argument("--force-launch", action="store_true",
                     help="start the rank processes through the launcher even for --gpus 1 (test of the launcher)")
     args = ap.parse_args()
@@ -478,31 +516,34 @@ def main():
     del Kfac
     t0 = time.perf_counter()
     solver = eg.IRAM(N=N, m=args.m, mode="buckling", ctx=ctx)
-    lam, Phi = solver.solve(G, K, factor, sigma)
+    # (a plain run solves once, on the matrices as they sit in HBM: what the solver of the timed steps is given in
+    # either kind of run; the eigensolver's kernels are deterministic, so the eigenpairs are the same bits)
+    lam, Phi = solver.solve(G, K, factor, sigma) if args.full else solver.solve(dG, dK, factor, sigma)
     ctx.sync()
     timing["eigensolve_s"] = time.perf_counter() - t0
     eig_count = factor.count
-    # the same eigensolve once more, as every design point after the first sees it (work blocks, page-locked result
-    # buffers and the coefficient slots come from the pools the first one filled)
-    # (twice: the second large result of a size is the one that page-locks its buffer, the third finds it in the pool)
-    del lam, Phi
-    for _ in range(2):
-        solver = lam = Phi = None
-        solver = eg.IRAM(N=N, m=args.m, mode="buckling", ctx=ctx)
-        ctx.sync()
-        t0 = time.perf_counter()
-        lam, Phi = solver.solve(dG, dK, factor, sigma)     # (the matrices as they sit in HBM: no upload, as after a device assembly)
-        ctx.sync()
-        timing["eigensolve_repeat_s"] = time.perf_counter() - t0
-    factor.count = eig_count
+    if args.full:
+        # the same eigensolve once more, as every design point after the first sees it (work blocks, page-locked result
+        # buffers and the coefficient slots come from the pools the first one filled)
+        # (twice: the second large result of a size is the one that page-locks its buffer, the third finds it in the pool)
+        del lam, Phi
+        for _ in range(2):
+            solver = lam = Phi = None
+            solver = eg.IRAM(N=N, m=args.m, mode="buckling", ctx=ctx)
+            ctx.sync()
+            t0 = time.perf_counter()
+            lam, Phi = solver.solve(dG, dK, factor, sigma)     # (the matrices as they sit in HBM: no upload, as after a device assembly)
+            ctx.sync()
+            timing["eigensolve_repeat_s"] = time.perf_counter() - t0
+        factor.count = eig_count
     eig_info = {"block_size": int(getattr(solver, "block_size", 1)), "internal_basis": int(getattr(solver, "internal_basis", args.m)),
                 "restarts": int(solver.n_restarts), "sweeps": int(getattr(solver, "sweeps", eig_count)),
                 "factor_applications": int(eig_count), "extra_pairs_for_deflation": int(solver.n_extra),
                 # the true-residual check of the returned pairs inside solve(): one N-column sweep + product, inside
                 # eigensolve_s but counted neither in `sweeps` nor in `factor_applications` (a check, not a solve)
                 "residual_check_sweeps": 1, "residual_check_columns": int(N)}
-    log(rank, f"eigensolve: {timing['eigensolve_s']:.2f}s (repeated: {timing['eigensolve_repeat_s']:.2f}s), {eig_info}; "
-              f"BLF = {lam[:4]} ... {lam[-1]:.4f}")
+    log(rank, f"eigensolve: {timing['eigensolve_s']:.2f}s (repeated: {timing.get('eigensolve_repeat_s', float('nan')):.2f}s), "
+              f"{eig_info}; BLF = {lam[:4]} ... {lam[-1]:.4f}")
 
     rng = np.random.default_rng(1)
     Phib = rng.uniform(size=(n, N))
@@ -557,6 +598,8 @@ def main():
         return
     if args.dump_dfdx:
         np.save(args.dump_dfdx, dfdx)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dpsi, data, dfdx)
     if args.trace:
         import eigd_amd.adjoint as adj
 
@@ -603,6 +646,45 @@ def main():
         pr.disable()
         with open(args.pyprofile, "w") as fh:
             pstats.Stats(pr, stream=fh).sort_stats("cumulative").print_stats(45)
+    out = {
+        "metric": "adjoint_mode_derivatives_per_sec",
+        "value": round(value, 3),
+        "unit": "modes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"buckling {n / 1e6:.1f}M-dof Q4 column ({args.nx}x{args.ny} elements), {N} modes, "
+                               f"IRAM m={args.m} + sibk rtol={args.rtol:g} + tensor total derivative w.r.t. element densities",
+                   "n_dof": int(n), "nnz": int(K.nnz), "modes": N, "m": args.m, "sigma": round(float(sigma), 6),
+                   "ordering": args.ordering,
+                   "parallelism": f"modes sharded over {world} GPU(s), one RCCL all-reduce of df/dx per step"},
+        "preamble_s": {k: round(v, 3) for k, v in timing.items()},
+        "factor_sweeps_per_step": int(adj_count),
+        "sibk_iterations": sibk_iterations,
+        "eigensolve_sweeps": int(eig_count),
+        "eigensolver": eig_info,
+        "lock_step": {"recurrence": last_round.get("recurrence"),
+                      "cg": {key[3:]: last_round.get(key) for key in ("cg_steps", "cg_projections", "cg_projection_updates",
+                                                                      "cg_sweeps_for_nothing", "cg_waited_for",
+                                                                      "cg_restarted_modes", "cg_solution")},
+                      "steps_per_gram_schmidt_pass": last_round.get("steps_per_pass"),
+                      "inner_projections": last_round.get("inner_projections"),
+                      "cycles": last_round.get("gs_cycles"),
+                      "correcting_gram_schmidt_passes": last_round.get("gs_correcting_passes"),
+                      "post_gs_projections_measured": last_round.get("post_gs_projections"),
+                      "post_gs_updates_applied": last_round.get("post_gs_updates_applied"),
+                      "cycles_enqueued_for_nothing": last_round.get("cycles_enqueued_for_nothing"),
+                      "cycles_waited_for": last_round.get("cycles_waited_for")},
+    }
+    if not args.full:               # a plain run: the headline and what the timed steps counted, nothing more
+        print(json.dumps(out), flush=True)
+        return
     # ------------------------------------------------------------------ the reference's call surface: numpy in, numpy out
     # (this leg runs BEFORE the Arnoldi and scaling-model legs: behind the Arnoldi leg's downloads and release_workspaces()
     # both transfers of the numpy step ran at half their rate on the same box -- 9.6 + 8.8 ms against 4.7 + 4.7 -- although
@@ -942,24 +1024,7 @@ def main():
         accuracy["dfdx_rel_err_gpu_vs_cpu"] = cpu.pop("dfdx_rel_err_gpu_vs_cpu")
         accuracy["psi_rel_err_gpu_vs_cpu"] = cpu["psi_rel_err_gpu_vs_cpu"]
 
-    out = {
-        "metric": "adjoint_mode_derivatives_per_sec",
-        "value": round(value, 3),
-        "unit": "modes/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"buckling {n / 1e6:.1f}M-dof Q4 column ({args.nx}x{args.ny} elements), {N} modes, "
-                               f"IRAM m={args.m} + sibk rtol={args.rtol:g} + tensor total derivative w.r.t. element densities",
-                   "n_dof": int(n), "nnz": int(K.nnz), "modes": N, "m": args.m, "sigma": round(float(sigma), 6),
-                   "ordering": args.ordering,
-                   "parallelism": f"modes sharded over {world} GPU(s), one RCCL all-reduce of df/dx per step"},
+    out.update({
         "roofline": roofline,
         "spmv": spmv,
         "spmm": spmm,
@@ -967,32 +1032,16 @@ def main():
         "numpy_api": numpy_api,
         "accuracy": accuracy,
         "preamble_s": {k: round(v, 3) for k, v in timing.items()},
-        "factor_sweeps_per_step": int(adj_count),
-        "sibk_iterations": sibk_iterations,
         "arnoldi_form": arnoldi_form,
         "scaling_model": scaling_model,
         "scaling_model_c5": None,
         "extras0": extras0,
-        "eigensolve_sweeps": int(eig_count),
-        "eigensolver": eig_info,
-        "lock_step": {"recurrence": last_round.get("recurrence"),
-                      "cg": {key[3:]: last_round.get(key) for key in ("cg_steps", "cg_projections", "cg_projection_updates",
-                                                                      "cg_sweeps_for_nothing", "cg_waited_for",
-                                                                      "cg_restarted_modes", "cg_solution")},
-                      "steps_per_gram_schmidt_pass": last_round.get("steps_per_pass"),
-                      "inner_projections": last_round.get("inner_projections"),
-                      "cycles": last_round.get("gs_cycles"),
-                      "correcting_gram_schmidt_passes": last_round.get("gs_correcting_passes"),
-                      "post_gs_projections_measured": last_round.get("post_gs_projections"),
-                      "post_gs_updates_applied": last_round.get("post_gs_updates_applied"),
-                      "cycles_enqueued_for_nothing": last_round.get("cycles_enqueued_for_nothing"),
-                      "cycles_waited_for": last_round.get("cycles_waited_for")},
         # one design point of an optimisation loop as the reference's harness runs it (buckling.py:548-632, 874-986):
         # assembly + factorisation (device: K, G(u), K + sigma G, numeric factor) + eigensolve + the timed step
         # (a design point after the first: device assembly + refactorisation and the eigensolve as repeated)
         "design_point_s": round(timing["device_assemble_and_refactor_s"] + timing["eigensolve_repeat_s"] + ms_per_step * 1e-3, 4),
         "first_design_point_s": round(timing["device_assemble_and_refactor_s"] + timing["eigensolve_s"] + ms_per_step * 1e-3, 4),
-    }
+    })
     out["design_point_modes_per_s"] = round(N / out["design_point_s"], 3)
     if extras0 is not None:
         extras0["design_point_s"] = round(timing["device_assemble_and_refactor_s"] + extras0["eigensolve_s"]

@@ -516,7 +516,7 @@ def test_bench_launcher_starts_rank_processes(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-launch", "--nx", "60", "--ny", "60",
-           "--modes", "4", "--m", "20", "--steps", "1", "--warmup", "0", "--cpu-sample", "none", "--no-fd-check",
+           "--modes", "4", "--m", "20", "--steps", "1", "--warmup", "0", "--full", "--cpu-sample", "none", "--no-fd-check",
            "--numpy-steps", "0", "--spmv-reps", "4"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -524,8 +524,52 @@ def test_bench_launcher_starts_rank_processes(tmp_path):
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["config"]["modes"] == 4
 
 
-_SMALL_BENCH = ["--nx", "60", "--ny", "60", "--modes", "4", "--m", "20", "--steps", "1", "--warmup", "0", "--cpu-sample",
-                "none", "--no-fd-check", "--numpy-steps", "0", "--spmv-reps", "4"]
+_SMALL_BENCH = ["--nx", "60", "--ny", "60", "--modes", "4", "--m", "20", "--steps", "1", "--warmup", "0", "--full",
+                "--cpu-sample", "none", "--no-fd-check", "--numpy-steps", "0", "--spmv-reps", "4"]
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_returned(tmp_path):
+    """
+    A plain run (no --full) prints the headline line for exactly --steps timed steps and nothing of the extra legs;
+    --dump-outputs writes the last step's psi sample, df/dx and pair coefficients as float64 .npy files, the same bits
+    from run to run, and what a --full run (which repeats the eigensolve) computes.
+    """
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--nx", "60", "--ny", "60", "--modes", "4", "--m", "20", "--steps", "3", "--warmup", "1"]
+    dumps, lines = {}, {}
+    for tag, extra in (("plain", []), ("again", []),
+                       ("full", ["--full", "--cpu-sample", "none", "--no-fd-check", "--numpy-steps", "0", "--spmv-reps", "4",
+                                 "--no-arnoldi-leg", "--no-scaling-model", "--no-extras0-leg"])):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dump-outputs", str(d)] + small + extra,
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        lines[tag] = json.loads(out.stdout.strip().splitlines()[-1])
+        dumps[tag] = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+    line = lines["plain"]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert line[key] == lines["full"][key]
+    assert not {"roofline", "spmv", "cpu_baseline", "accuracy", "design_point_s"} & set(line)
+    assert {"roofline", "spmv", "accuracy", "design_point_s"} <= set(lines["full"])
+    got = dumps["plain"]
+    assert {"psi_sample", "psi_sample_rows", "dfdx"} <= set(got) <= {"psi_sample", "psi_sample_rows", "dfdx", "adj_corr_data"}
+    assert all(a.dtype == np.float64 and a.size > 0 for a in got.values())      # no empty output
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["psi_sample"].shape == (got["psi_sample_rows"].size, 4)
+    assert "adj_corr_data" not in got or got["adj_corr_data"].shape[1] == 4
+    for tag in ("again", "full"):
+        assert set(dumps[tag]) == set(got), tag
+    assert np.all(np.isfinite(got["psi_sample"])) and np.linalg.norm(got["dfdx"]) > 0
+    for name, a in got.items():
+        assert np.array_equal(dumps["again"][name], a), name
+        assert dumps["full"][name].shape == a.shape and relerr(dumps["full"][name], a) <= 1e-12, name
 
 
 def test_bench_launcher_ends_when_a_rank_dies_before_the_communicator():

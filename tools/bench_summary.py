@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""the fields of a bench.py JSON line one looks at first.  Usage: bench_summary.py file.json"""
+"""the fields of a `bench.py --full` JSON line one looks at first.  Usage: bench_summary.py file.json"""
 import json
 import sys
 

@@ -10,7 +10,7 @@ python3 tools/step_breakdown.py $out/stats > $out/step_breakdown.txt || exit 1
 rm -rf $out/stats
 cd $root
 echo "[evidence] bench c3" 
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_c3.json 2> $out/bench_c3.err || { tail -5 $out/bench_c3.err; exit 1; }
+timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_c3.json 2> $out/bench_c3.err || { tail -5 $out/bench_c3.err; exit 1; }
 echo "[evidence] emulated ranks"
 bash tools/rank_variants.sh $out/emulated_ranks_2.txt 1/2 EIGD_X=0 > /dev/null || exit 1
 bash tools/rank_variants.sh $out/emulated_ranks_4.txt 3/4 EIGD_X=0 > /dev/null || exit 1
