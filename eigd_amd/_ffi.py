@@ -72,6 +72,9 @@ _SIGNATURES = {
     "eigd_factor_lane_create": [c_vp, c_vp, P(c_vp)],
     "eigd_factor_lane_free": [c_vp],
     "eigd_factor_lane_solve_to": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl],
+    "eigd_sweep_variants": [c_vp, c_int, P(c_int)],
+    "eigd_factor_record_sweeps": [c_vp, c_int],
+    "eigd_factor_sweep_record": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, P(c_int)],
     "eigd_factor_stats": [c_vp, c_vp, c_int],
     "eigd_factor_solve_bytes": [c_vp, c_int, P(c_dbl)],
     "eigd_gemm_tn": [c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_int, c_vp],

@@ -2002,6 +2002,54 @@ __global__ __launch_bounds__(kThreads) void pack_frag_kernel(FrontArrays fa, con
   }
 }
 
+// ------------------------------------------------------------------ launch record of the sweeps
+// Every launch of sweep() goes through EIGD_SWEEP_LAUNCH, which names the kernel with its resolved template arguments
+// the way a kernel trace prints them ("fwd_thin_kernel<32, 12, 2, 2, true>").  Each launch site registers that name
+// when the library is loaded (static member of SweepVariant, instantiated by the site), so the table is exactly the
+// set of variants the compiled sweeps can launch, unreachable arms included.  A solver object with recording on
+// appends (variant, level, columns) of every launch of its most recent solve; off, a launch costs one branch.
+inline std::vector<std::string>& sweep_variant_table() {
+  static std::vector<std::string> t;
+  return t;
+}
+inline std::string sweep_targ(int v) { return std::to_string(v); }
+inline std::string sweep_targ(bool v) { return v ? "true" : "false"; }
+template <typename... A>
+int register_sweep_variant(const char* family, A... a) {
+  std::string name = family;
+  if constexpr (sizeof...(A) > 0) {
+    const char* sep = "<";
+    ((name += sep, name += sweep_targ(a), sep = ", "), ...);
+    name += ">";
+  }
+  std::vector<std::string>& t = sweep_variant_table();
+  for (size_t i = 0; i < t.size(); ++i)
+    if (t[i] == name) return static_cast<int>(i);  // (two arms of the dispatch may launch one instantiation)
+  t.push_back(name);
+  return static_cast<int>(t.size()) - 1;
+}
+template <const char* FAM, auto... A>
+struct SweepVariant {
+  static const int id;
+};
+template <const char* FAM, auto... A>
+const int SweepVariant<FAM, A...>::id = register_sweep_variant(FAM, A...);
+constexpr char fwd_wave_kernel_family[] = "fwd_wave_kernel";
+constexpr char bwd_wave_kernel_family[] = "bwd_wave_kernel";
+constexpr char fwd_thin_kernel_family[] = "fwd_thin_kernel";
+constexpr char bwd_thin_kernel_family[] = "bwd_thin_kernel";
+constexpr char fwd_level_kernel_family[] = "fwd_level_kernel";
+constexpr char bwd_level_kernel_family[] = "bwd_level_kernel";
+constexpr char v1_assemble_kernel_family[] = "v1_assemble_kernel";
+constexpr char overflow_sum_kernel_family[] = "overflow_sum_kernel";
+
+struct SweepLaunch {
+  int variant, level, kb;
+};
+struct SweepRecord {
+  std::vector<SweepLaunch> launches;  // of the most recent solve
+};
+
 }  // namespace eigd
 
 using namespace eigd;
@@ -2066,6 +2114,8 @@ struct eigd_factor {
   size_t bytes = 0;
   std::vector<int> ea_split;  // per (level, slot): grid.y of the extend-add launches
   int64_t data_len = 0;
+  bool record_sweeps = false;  // solves of the factor and of its lanes record their launches (tests)
+  SweepRecord rec;             // ... those of the factor's own stream
 
   FrontArrays fa() const {
     FrontArrays a;
@@ -2216,9 +2266,18 @@ int pre_assembly_min_workgroups() {
 // columns otherwise go through the 16-column MFMA kernels.
 constexpr int kWaveMaxKpt = 2;   // widest sweep (units of 4 columns) whose single-tile fronts use the readlane wave kernels
 
+// one launch of the sweep: KERNEL<TARGS...> (every template argument spelled out, defaults included: they are part of
+// the variant's name), recorded at level l with kb columns when rec is set
+#define EIGD_UNPAREN(...) __VA_ARGS__
+#define EIGD_SWEEP_LAUNCH(KERNEL, TARGS, ...)                                                               \
+  do {                                                                                                      \
+    if (rec) rec->launches.push_back({SweepVariant<KERNEL##_family, EIGD_UNPAREN TARGS>::id, l, kb});      \
+    hipLaunchKernelGGL((KERNEL<EIGD_UNPAREN TARGS>), __VA_ARGS__);                                         \
+  } while (0)
+
 template <int KPT>
 int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, int* wT, const double* dIn, int ldin,
-          double* dX, int ldx, int kb, double alpha) {
+          double* dX, int ldx, int kb, double alpha, SweepRecord* rec) {
   const Symbolic& s = *f->sym;
   const FrontArrays fa = f->fa();
   // every sweep width (KB = 4, 8, 16, 32 columns) has its own set of carry planes: rows are KB wide and the
@@ -2259,6 +2318,7 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
     if (nov > 0) {
       const int first = f->ov_lvl_ptr[l];
       const int64_t plane = f->v_rows * KB;
+      if (rec) rec->launches.push_back({SweepVariant<overflow_sum_kernel_family>::id, l, kb});
       hipLaunchKernelGGL(overflow_sum_kernel, dim3((nov * kb + 255) / 256), dim3(256), 0, st, nov, f->d_ov_dst + first,
                          f->d_ov_ptr + first, f->d_ov_src, kb, KB, wV + (f->nslot - 1) * plane, wV + f->nslot * plane);
       EIGD_LAUNCH_CHECK();
@@ -2272,13 +2332,13 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
       if (nwave > 0) {  // narrow sweep: one wave per tile of the single-tile fronts, two waves per front
         const WgRec* recs = f->d_wave_wg + f->h_wave_ptr[l];
         if (leaf)
-          hipLaunchKernelGGL((fwd_wave_kernel<KB, 0, 2>), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin, alpha, wV,
+          EIGD_SWEEP_LAUNCH(fwd_wave_kernel, (KB, 0, 2), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin, alpha, wV,
                              wY, kb);
         else if (two)
-          hipLaunchKernelGGL((fwd_wave_kernel<KB, 2, 2>), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin, alpha, wV,
+          EIGD_SWEEP_LAUNCH(fwd_wave_kernel, (KB, 2, 2), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin, alpha, wV,
                              wY, kb);
         else
-          hipLaunchKernelGGL((fwd_wave_kernel<KB, kMaxS + 1, 2>), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin,
+          EIGD_SWEEP_LAUNCH(fwd_wave_kernel, (KB, kMaxS + 1, 2), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin,
                              alpha, wV, wY, kb);
         EIGD_LAUNCH_CHECK();
         narrow = true;
@@ -2291,10 +2351,10 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
 #define EIGD_THIN_FWD(NKS, NSLV, WPFV)                                                                                   \
   do {                                                                                                                   \
     if (fa.tri)                                                                                                          \
-      hipLaunchKernelGGL((fwd_thin_kernel<KB, NKS, NSLV, WPFV, true>), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
+      EIGD_SWEEP_LAUNCH(fwd_thin_kernel, (KB, NKS, NSLV, WPFV, true), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
                          alpha, wV, wY, kb, f->d_Fb);                                                                    \
     else                                                                                                                 \
-      hipLaunchKernelGGL((fwd_thin_kernel<KB, NKS, NSLV, WPFV, false>), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
+      EIGD_SWEEP_LAUNCH(fwd_thin_kernel, (KB, NKS, NSLV, WPFV, false), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
                          alpha, wV, wY, kb, f->d_Fb);                                                                    \
   } while (0)
         if (!leaf && two && nks >= 12) {
@@ -2346,13 +2406,13 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
         return static_cast<unsigned>(sizeof(double) * (kd + 1) * ((KPT == 4 ? 0 : TLD) + Tile<KPT>::BLD));
       };
       if (leaf)
-        hipLaunchKernelGGL((fwd_level_kernel<KPT, true, 0>), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st, fa, la,
+        EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, true, 0, false, false), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st, fa, la,
                            sF, sT, dIn, ldin, alpha, wV, wY);
       else if (two)
-        hipLaunchKernelGGL((fwd_level_kernel<KPT, true, 2>), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st, fa, la,
+        EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, true, 2, false, false), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st, fa, la,
                            sF, sT, dIn, ldin, alpha, wV, wY);
       else
-        hipLaunchKernelGGL((fwd_level_kernel<KPT, true, kMaxS + 1>), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st,
+        EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, true, kMaxS + 1, false, false), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st,
                            fa, la, sF, sT, dIn, ldin, alpha, wV, wY);
       EIGD_LAUNCH_CHECK();
     }
@@ -2363,28 +2423,28 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
         if (npre > 0) {  // v1 of the level's fronts once, then row-tile workgroups that read it as it lies
           const WgRec* pre = f->d_pre_wg + f->h_pre_ptr[l];
           if (two) {
-            hipLaunchKernelGGL((v1_assemble_kernel<KPT, 2>), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin, alpha, wV,
+            EIGD_SWEEP_LAUNCH(v1_assemble_kernel, (KPT, 2), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin, alpha, wV,
                                wV1, kb);
-            hipLaunchKernelGGL((fwd_level_kernel<KPT, false, 2, true, true>), multi_grid(nwg - nsingle), dim3(kThreads),
+            EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, true, true), multi_grid(nwg - nsingle), dim3(kThreads),
                                lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
           } else {
-            hipLaunchKernelGGL((v1_assemble_kernel<KPT, kMaxS + 1>), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin,
+            EIGD_SWEEP_LAUNCH(v1_assemble_kernel, (KPT, kMaxS + 1), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin,
                                alpha, wV, wV1, kb);
-            hipLaunchKernelGGL((fwd_level_kernel<KPT, false, kMaxS + 1, true, true>), multi_grid(nwg - nsingle),
+            EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, true, true), multi_grid(nwg - nsingle),
                                dim3(kThreads), lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
           }
         } else if (two)
-          hipLaunchKernelGGL((fwd_level_kernel<KPT, false, 2, true>), multi_grid(nwg - nsingle), dim3(kThreads),
+          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, true, false), multi_grid(nwg - nsingle), dim3(kThreads),
                              lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
         else
-          hipLaunchKernelGGL((fwd_level_kernel<KPT, false, kMaxS + 1, true>), multi_grid(nwg - nsingle),
+          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, true, false), multi_grid(nwg - nsingle),
                              dim3(kThreads), lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
       } else {
         if (two)
-          hipLaunchKernelGGL((fwd_level_kernel<KPT, false, 2>), multi_grid(nwg - nsingle), dim3(kThreads),
+          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, false, false), multi_grid(nwg - nsingle), dim3(kThreads),
                              lds_bytes(TW), st, fa, la, sF, sT, dIn, ldin, alpha, wV, wY);
         else
-          hipLaunchKernelGGL((fwd_level_kernel<KPT, false, kMaxS + 1>), multi_grid(nwg - nsingle), dim3(kThreads),
+          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, false, false), multi_grid(nwg - nsingle), dim3(kThreads),
                              lds_bytes(TW), st, fa, la, sF, sT, dIn, ldin, alpha, wV, wY);
       }
       EIGD_LAUNCH_CHECK();
@@ -2403,20 +2463,20 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
       const LevelArgs la = level_args(f->d_bwd_wg + f->h_bwd_ptr[l] + nsb, TW, nwg - nsb, true);
       if constexpr (Tile<KPT>::kMfma) {
         if (KPT >= 8 && f->h_bwd_mxbs[l] <= kLidxMax)
-          hipLaunchKernelGGL((bwd_level_kernel<KPT, false, true, (KPT >= 8)>), multi_grid(nwg - nsb), dim3(kThreads),
+          EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, true, (KPT >= 8)), multi_grid(nwg - nsb), dim3(kThreads),
                              lds_frag + 4u * static_cast<unsigned>((f->h_bwd_mxbs[l] + 3) & ~3), st, fa, la, sF, sT, f->d_Bm,
                              wY, dX, ldx);
         else
-          hipLaunchKernelGGL((bwd_level_kernel<KPT, false, true>), multi_grid(nwg - nsb), dim3(kThreads), lds_frag, st, fa,
+          EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, true, false), multi_grid(nwg - nsb), dim3(kThreads), lds_frag, st, fa,
                              la, sF, sT, f->d_Bm, wY, dX, ldx);
       }
       else
-        hipLaunchKernelGGL((bwd_level_kernel<KPT, false>), multi_grid(nwg - nsb), dim3(kThreads), lds_bytes(TW), st, fa, la, sF,
+        EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, false, false), multi_grid(nwg - nsb), dim3(kThreads), lds_bytes(TW), st, fa, la, sF,
                            sT, f->d_Ft, wY, dX, ldx);
       EIGD_LAUNCH_CHECK();
     }
     if (narrow) {
-      hipLaunchKernelGGL(bwd_wave_kernel<KB>, dim3(nwave), dim3(64), 0, st, fa, f->d_wave_wg + f->h_wave_ptr[l], f->d_Ft,
+      EIGD_SWEEP_LAUNCH(bwd_wave_kernel, (KB), dim3(nwave), dim3(64), 0, st, fa, f->d_wave_wg + f->h_wave_ptr[l], f->d_Ft,
                          wY, dX, ldx, kb);
       EIGD_LAUNCH_CHECK();
     } else if (thin) {
@@ -2426,10 +2486,10 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
 #define EIGD_THIN_BWD(NOB, CHV)                                                                                   \
   do {                                                                                                            \
     if (fa.tri)                                                                                                   \
-      hipLaunchKernelGGL((bwd_thin_kernel<KB, NOB, CHV, true>), dim3(nwave), dim3(64), 0, st, fa, recs, f->d_Ft, wY, \
+      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, true), dim3(nwave), dim3(64), 0, st, fa, recs, f->d_Ft, wY, \
                          dX, ldx, kb);                                                                            \
     else                                                                                                          \
-      hipLaunchKernelGGL((bwd_thin_kernel<KB, NOB, CHV, false>), dim3(nwave), dim3(64), 0, st, fa, recs, f->d_Ft, \
+      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, false), dim3(nwave), dim3(64), 0, st, fa, recs, f->d_Ft, \
                          wY, dX, ldx, kb);                                                                        \
   } while (0)
         if (nks == 4)
@@ -2442,13 +2502,15 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
         EIGD_LAUNCH_CHECK();
       }
     } else if (nsb > 0) {  // single-column-tile fronts: LDS tiles as tall as the level needs
-      hipLaunchKernelGGL((bwd_level_kernel<KPT, true>), dim3(nsb), dim3(kThreads), lds_bytes(f->h_bwd_kd[l]), st, fa,
+      EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, true, false, false), dim3(nsb), dim3(kThreads), lds_bytes(f->h_bwd_kd[l]), st, fa,
                          level_args(f->d_bwd_wg + f->h_bwd_ptr[l], f->h_bwd_kd[l]), sF, sT, f->d_Ft, wY, dX, ldx);
       EIGD_LAUNCH_CHECK();
     }
   }
   return EIGD_OK;
 }
+#undef EIGD_SWEEP_LAUNCH
+#undef EIGD_UNPAREN
 
 }  // namespace
 
@@ -3029,19 +3091,21 @@ int eigd_factor_solve(eigd_factor* f, double* dX, int ldx, int k, double alpha) 
 }
 
 static int solve_blocks(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, int* wT, const double* dIn,
-                        int ldin, double* dOut, int ldout, int k, double alpha) {
+                        int ldin, double* dOut, int ldout, int k, double alpha, SweepRecord& record) {
   EIGD_REQUIRE(f && dIn && dOut, "null argument");
   EIGD_REQUIRE(k >= 1 && ldin >= k && ldout >= k, "bad block shape k=%d ldin=%d ldout=%d", k, ldin, ldout);
+  SweepRecord* rec = f->record_sweeps ? &record : nullptr;
+  if (rec) rec->launches.clear();
   for (int c0 = 0; c0 < k; c0 += KBMAX) {
     const int kb = std::min(KBMAX, k - c0);
     int rc;
     // 5 to 8 columns go through the 16-column kernels, whose single-tile levels are MFMA wave kernels (1.26 -> 1.09 ms)
     if (kb <= 4)
-      rc = sweep<1>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha);
+      rc = sweep<1>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     else if (kb <= 16)
-      rc = sweep<4>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha);
+      rc = sweep<4>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     else
-      rc = sweep<8>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha);
+      rc = sweep<8>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     if (rc != EIGD_OK) return rc;
   }
   return EIGD_OK;
@@ -3049,7 +3113,7 @@ static int solve_blocks(eigd_factor* f, hipStream_t st, double* wV, double* wY, 
 
 int eigd_factor_solve_to(eigd_factor* f, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha) {
   EIGD_REQUIRE(f, "null argument");
-  return solve_blocks(f, f->ctx->stream, f->d_V, f->d_Y, f->d_P, f->d_tickets, dIn, ldin, dOut, ldout, k, alpha);
+  return solve_blocks(f, f->ctx->stream, f->d_V, f->d_Y, f->d_P, f->d_tickets, dIn, ldin, dOut, ldout, k, alpha, f->rec);
 }
 
 // A lane = a second set of sweep workspaces bound to another context (stream) of the same device: sweeps of
@@ -3059,6 +3123,7 @@ struct eigd_lane {
   eigd_ctx* ctx = nullptr;
   double *V = nullptr, *Y = nullptr, *P = nullptr;
   int* tickets = nullptr;
+  SweepRecord rec;  // launches of the lane's most recent solve (when its factor records them)
 };
 
 int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out) {
@@ -3099,7 +3164,34 @@ int eigd_factor_lane_free(eigd_lane* l) {
 
 int eigd_factor_lane_solve_to(eigd_lane* l, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha) {
   EIGD_REQUIRE(l, "null argument");
-  return solve_blocks(l->f, l->ctx->stream, l->V, l->Y, l->P, l->tickets, dIn, ldin, dOut, ldout, k, alpha);
+  return solve_blocks(l->f, l->ctx->stream, l->V, l->Y, l->P, l->tickets, dIn, ldin, dOut, ldout, k, alpha, l->rec);
+}
+
+int eigd_sweep_variants(const char** names, int cap, int* count) {
+  EIGD_REQUIRE(count && (cap <= 0 || names), "null argument");
+  const std::vector<std::string>& t = sweep_variant_table();
+  *count = static_cast<int>(t.size());
+  for (int i = 0; i < cap && i < *count; ++i) names[i] = t[static_cast<size_t>(i)].c_str();
+  return EIGD_OK;
+}
+
+int eigd_factor_record_sweeps(eigd_factor* f, int on) {
+  EIGD_REQUIRE(f, "null argument");
+  f->record_sweeps = on != 0;
+  return EIGD_OK;
+}
+
+int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int* level, int* kb, int cap, int* count) {
+  EIGD_REQUIRE(f && count && (cap <= 0 || (variant && level && kb)), "null argument");
+  EIGD_REQUIRE(!lane || lane->f == f, "the lane belongs to another factor");
+  const std::vector<SweepLaunch>& r = (lane ? lane->rec : f->rec).launches;
+  *count = static_cast<int>(r.size());
+  for (int i = 0; i < cap && i < *count; ++i) {
+    variant[i] = r[static_cast<size_t>(i)].variant;
+    level[i] = r[static_cast<size_t>(i)].level;
+    kb[i] = r[static_cast<size_t>(i)].kb;
+  }
+  return EIGD_OK;
 }
 
 int eigd_factor_stats(eigd_factor* f, double* out, int nout) {

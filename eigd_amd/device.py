@@ -5,6 +5,7 @@ blocks and stacks of them), CSR matrices, symbolic analysis and the numeric fact
 Nothing here computes on the host; every method is one call into libeigd_hip.so.
 """
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -1065,6 +1066,15 @@ class Symbolic:
         return out[:ln]
 
 
+def sweep_variants():
+    """names of every kernel variant the compiled sweeps can launch, e.g. 'fwd_thin_kernel<32, 12, 2, 2, true>' (host only)"""
+    cnt = C.c_int()
+    call("eigd_sweep_variants", None, 0, C.byref(cnt))
+    names = (C.c_char_p * max(cnt.value, 1))()
+    call("eigd_sweep_variants", names, cnt.value, C.byref(cnt))
+    return [names[i].decode() for i in range(cnt.value)]
+
+
 class Factor:
     """Numeric LL^T factor of a symmetric positive definite CSR matrix on the device."""
 
@@ -1150,6 +1160,7 @@ class Factor:
         if X.ctx is not self.ctx:
             return self.solve_to(X, X, alpha)
         call("eigd_factor_solve", self.h, X.ptr, X.ld, X.k, float(alpha))
+        self._note_sweep(None)
         return X
 
     def solve_to(self, Xin, Xout, alpha=1.0):
@@ -1158,10 +1169,46 @@ class Factor:
             raise ValueError("shape mismatch in factor solve")
         if Xout.ctx is self.ctx:
             call("eigd_factor_solve_to", self.h, Xin.ptr, Xin.ld, Xout.ptr, Xout.ld, Xin.k, float(alpha))
+            self._note_sweep(None)
         else:
-            call("eigd_factor_lane_solve_to", self._lane(Xout.ctx), Xin.ptr, Xin.ld, Xout.ptr, Xout.ld, Xin.k,
-                 float(alpha))
+            lane = self._lane(Xout.ctx)
+            call("eigd_factor_lane_solve_to", lane, Xin.ptr, Xin.ld, Xout.ptr, Xout.ld, Xin.k, float(alpha))
+            self._note_sweep(lane)
         return Xout
+
+    def last_sweep_record(self, ctx=None):
+        """launches of the most recent solve on ``ctx`` (None: the factor's own) as (variant name, level, columns);
+        empty unless recording is on (sweep_record)"""
+        lane = None if ctx is None or ctx is self.ctx else self._lane(ctx)
+        return self._sweep_record_of(lane)
+
+    def _sweep_record_of(self, lane):
+        cnt = C.c_int()
+        call("eigd_factor_sweep_record", self.h, lane, None, None, None, 0, C.byref(cnt))
+        var, lvl, kb = (np.zeros(max(cnt.value, 1), dtype=np.int32) for _ in range(3))
+        call("eigd_factor_sweep_record", self.h, lane, hptr(var), hptr(lvl), hptr(kb), cnt.value, C.byref(cnt))
+        names = sweep_variants()
+        return [(names[v], int(l), int(k)) for v, l, k in zip(var[:cnt.value], lvl[:cnt.value], kb[:cnt.value])]
+
+    def _note_sweep(self, lane):
+        rec = self.__dict__.get("_sweep_log")
+        if rec is not None:
+            rec.extend(self._sweep_record_of(lane))
+
+    @contextlib.contextmanager
+    def sweep_record(self):
+        """
+        ``with F.sweep_record() as rec:`` -- every solve of the factor (and of its lanes) inside the block appends its
+        kernel launches to ``rec`` as (variant name, level, columns), in launch order; see device.sweep_variants
+        """
+        rec = []
+        call("eigd_factor_record_sweeps", self.h, 1)
+        self._sweep_log = rec
+        try:
+            yield rec
+        finally:
+            self._sweep_log = None
+            call("eigd_factor_record_sweeps", self.h, 0)
 
     def _lane(self, ctx):
         lanes = self.__dict__.setdefault("_lanes", {})

@@ -132,6 +132,18 @@ int eigd_factor_solve_to(eigd_factor* f, const double* dIn, int ldin, double* dO
 int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out);
 int eigd_factor_lane_free(eigd_lane* lane);
 int eigd_factor_lane_solve_to(eigd_lane* lane, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha);
+/* launch record of the sweeps (tests: which kernel variant ran at which level).
+ * eigd_sweep_variants: every kernel variant the compiled sweeps can launch, host only (no device needed); *count
+ *   variants, names[i] for i < min(count, cap) point to static strings "family<template arguments>" spelled the way a
+ *   kernel trace prints them, e.g. "fwd_thin_kernel<32, 12, 2, 2, true>".
+ * eigd_factor_record_sweeps: on != 0 makes every solve of the factor and of its lanes record its launches (off, the
+ *   default: one branch per launch).
+ * eigd_factor_sweep_record: the record of the most recent solve of the factor's own stream (lane == NULL) or of one
+ *   of its lanes: *count launches in launch order, the first min(count, cap) as (index into eigd_sweep_variants,
+ *   level of the assembly tree, columns of the sweep). */
+int eigd_sweep_variants(const char** names, int cap, int* count);
+int eigd_factor_record_sweeps(eigd_factor* f, int on);
+int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int* level, int* kb, int cap, int* count);
 /* stats: [0]=nnz(L) [1]=device bytes held [2]=flops of the numeric factorisation [3]=number of fronts
           [4]=negative pivots of P M P^T = L S L^T (inertia: eigenvalues of the pencil below the shift; 0 = SPD)
           [5]=static pivots [6]=planes of the sweeps' vector workspace (carry planes, + 1 where the right-hand sides of

@@ -399,8 +399,11 @@ def test_fronts_with_many_children_use_the_surplus_plane(ctx, nb, k):
     B = rng.normal(size=(A.shape[0], k))
     ref = splu(A.tocsc()).solve(B)
     for _ in range(2):  # twice: the planes' never-written entries must still read zero
-        X = F.solve_inplace(ctx.from_host(B)).get()
+        with F.sweep_record() as rec:
+            X = F.solve_inplace(ctx.from_host(B)).get()
         assert relerr(X, ref) < 1e-12
+        names = {v for v, _, _ in rec}
+        assert "overflow_sum_kernel" in names and any(", 5, " in v and v.startswith("fwd_") for v in names), names
     X1 = F.solve_inplace(ctx.from_host(B[:, :1])).get()  # another width on the same planes
     assert relerr(X1, ref[:, :1]) < 1e-12
 
@@ -439,8 +442,12 @@ def test_single_tile_fronts_with_long_borders(ctx, case):
     rng = np.random.default_rng(5)
     for k in (3, 12, 32):
         B = rng.normal(size=(A.shape[0], k))
-        X = F.solve_inplace(ctx.from_host(B)).get()
+        with F.sweep_record() as rec:
+            X = F.solve_inplace(ctx.from_host(B)).get()
         assert relerr(X, lu.solve(B)) < 1e-11, (case, k)
+        if k > 4:                                   # the single-tile backward tile kernel of the MFMA widths ran
+            kpt = 4 if k <= 16 else 8
+            assert f"bwd_level_kernel<{kpt}, true, false, false>" in {v for v, _, _ in rec}, (case, k)
     Xall = F.solve_inplace(ctx.from_host(B)).get()
     Xp = F.solve_inplace(ctx.from_host(B[:, 8:12])).get()
     assert np.array_equal(Xall[:, 8:12], Xp)
@@ -953,11 +960,16 @@ def test_multi_tile_fronts_with_ragged_sizes_through_the_fragment_kernels(ctx):
     lu = splu(A.tocsc())
     rng = np.random.default_rng(11)
     B = rng.normal(size=(A.shape[0], 32))
-    Xall = F.solve_inplace(ctx.from_host(B)).get()
-    assert relerr(Xall, lu.solve(B)) < 1e-11
-    for lo, hi in ((0, 1), (3, 7), (5, 13), (2, 18), (16, 32)):       # 4-, 8-, 16- and 32-column kernels
-        Xp = F.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
-        assert np.array_equal(Xall[:, lo:hi], Xp), (lo, hi)
+    with F.sweep_record() as rec:
+        Xall = F.solve_inplace(ctx.from_host(B)).get()
+        assert relerr(Xall, lu.solve(B)) < 1e-11
+        for lo, hi in ((0, 1), (3, 7), (5, 13), (2, 18), (16, 32)):       # 4-, 8-, 16- and 32-column kernels
+            Xp = F.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
+            assert np.array_equal(Xall[:, lo:hi], Xp), (lo, hi)
+    names = {v for v, _, _ in rec}
+    assert {"fwd_level_kernel<4, false, 2, true, false>", "fwd_level_kernel<8, false, 2, true, false>",
+            "bwd_level_kernel<4, false, true, false>", "bwd_level_kernel<8, false, true, true>",
+            "fwd_level_kernel<1, false, 2, false, false>", "bwd_level_kernel<1, false, false, false>"} <= names, names
     A2 = (A + 0.37 * sparse.identity(A.shape[0])).tocsr()
     F.refactor(A2)                                                     # the copies follow the numeric phase
     X2 = F.solve_inplace(ctx.from_host(B)).get()
@@ -1026,10 +1038,18 @@ def test_pre_assembled_right_hand_sides_are_bitwise_what_the_row_tile_workgroups
         F1 = Factor(ctx, Ai, symbolic=sym)
         assert F1.stats()["workspace_planes"] == F0.stats()["workspace_planes"] + 1
         assert (F0.stats()["negative_pivots"] > 20) == (shift is None)
+        nsl = 2 if case == "binary" else 5
         for lo, hi in ((0, 32), (3, 23), (0, 16), (7, 12), (0, 32), (1, 2)):
-            X0 = F0.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
-            X1 = F1.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
+            with F0.sweep_record() as rec0:
+                X0 = F0.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
+            with F1.sweep_record() as rec1:
+                X1 = F1.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
             assert np.array_equal(X0, X1), (case, shift, lo, hi)
+            n0, n1 = {v for v, _, _ in rec0}, {v for v, _, _ in rec1}
+            assert not any(v.startswith("v1_assemble_kernel") for v in n0)
+            if hi - lo > 4:                         # the MFMA widths pre-assemble
+                kpt = 4 if hi - lo <= 16 else 8
+                assert {f"v1_assemble_kernel<{kpt}, {nsl}>", f"fwd_level_kernel<{kpt}, false, {nsl}, true, true>"} <= n1, n1
         if shift == 0.0:
             assert relerr(X1, splu(Ai.tocsc()).solve(B[:, 1:2])) < 1e-11
             # a sweep lane (another stream's own vector workspaces, concurrent mode groups) has its own plane of v1
@@ -1043,9 +1063,10 @@ def test_pre_assembled_right_hand_sides_are_bitwise_what_the_row_tile_workgroups
 def test_long_borders_of_multi_tile_fronts_through_the_index_list_in_lds(ctx):
     """
     The 32-column backward level kernel keeps a front's border rows (its rows of the caller's block) in LDS, read once
-    -- 2048 entries in one round, the rest in a loop, up to 4096 -- where the narrower kernels hold eight of them per
-    lane in registers, requested two chain steps ahead.  A front with several column tiles and a border of 3226 rows:
-    32 columns against the residual, and bitwise against the 16-column kernels on the same columns.
+    -- 2048 entries in one round, the rest in a loop, up to kLidxMax = 7168 -- where the narrower kernels hold eight of
+    them per lane in registers, requested two chain steps ahead.  A front with several column tiles and a border of 3226
+    rows: 32 columns against the residual, and bitwise against the 16-column kernels on the same columns.  (Borders of
+    4097-7168 rows and beyond 7168, the fragment kernel without the list: tests/sweep_catalog.py, hub4600 / hub7300.)
     """
     from eigd_amd.device import Factor, Symbolic
 
@@ -1058,8 +1079,10 @@ def test_long_borders_of_multi_tile_fronts_through_the_index_list_in_lds(ctx):
     rng = np.random.default_rng(9)
     B = rng.normal(size=(A.shape[0], 32))
     for _ in range(2):
-        X = F.solve_inplace(ctx.from_host(B)).get()
+        with F.sweep_record() as rec:
+            X = F.solve_inplace(ctx.from_host(B)).get()
         assert np.linalg.norm(A @ X - B) / np.linalg.norm(B) < 1e-12
+        assert "bwd_level_kernel<8, false, true, true>" in {v for v, _, _ in rec}
     for lo, hi in ((0, 16), (5, 21), (20, 29)):
         Xp = F.solve_inplace(ctx.from_host(B[:, lo:hi])).get()
         assert np.array_equal(X[:, lo:hi], Xp), (lo, hi)
