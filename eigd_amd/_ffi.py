@@ -65,6 +65,7 @@ _SIGNATURES = {
     "eigd_symbolic_get_i32": [c_vp, C.c_char_p, c_vp, c_i64],
     "eigd_symbolic_get_i64": [c_vp, C.c_char_p, c_vp, c_i64],
     "eigd_factor_create": [c_vp, c_vp, c_vp, P(c_vp)],
+    "eigd_factor_create_lu": [c_vp, c_vp, c_vp, P(c_vp)],
     "eigd_factor_refactor": [c_vp, c_vp],
     "eigd_factor_free": [c_vp],
     "eigd_factor_solve": [c_vp, c_vp, c_int, c_int, c_dbl],

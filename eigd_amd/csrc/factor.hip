@@ -26,13 +26,21 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 #include "common.h"
 #include "symbolic.h"
 
 struct eigd_symbolic {
   eigd::Symbolic s;
+  std::mutex upper_lock;  // the upper scatter map of an LU factor is built on first demand (eigd_factor_create_lu)
 };
+
+// the upper scatter map of h, built once (analyses are shared between factors)
+static bool ensure_upper_map(eigd_symbolic* h) {
+  std::lock_guard<std::mutex> g(h->upper_lock);
+  return eigd::build_upper_map(h->s);
+}
 
 namespace eigd {
 
@@ -502,6 +510,185 @@ __global__ __launch_bounds__(kThreads) void syrk_kernel(FrontArrays fa, const in
     }
 }
 
+// ------------------------------------------------------------------ unsymmetric matrices: A = LL UU
+// SpLuOperator(..., symmetric=False) (reference 11-17: splu of any square matrix) on the same symbolic structure.  A
+// front's lower triangle (diagonal included) lives in F, its strictly upper triangle TRANSPOSED in a second
+// front-shaped buffer FU (FU(i, j) = A(j, i), i > j; its diagonal stays zero).  Both are then lower triangles of the
+// same shape, so the scatter, the extend-add, trsm_kernel and every inverse and copy kernel run on either buffer
+// unchanged.  Per panel step of W columns:
+//   panel   : P A11 = L U with partial pivoting INSIDE the W x W diagonal block (lu_inv_kernel); M_L = P^T L is a dense
+//             block, as on the Bunch-Kaufman path: only inv(M_L) and inv(U) leave the kernel, no row is moved outside
+//             the panel block, so the symbolic structure, v_src and the carry planes stay what they were
+//   F  : L21   = A21 inv(U)          trsm_kernel with inv(U)^T
+//   FU : U12^T = A12^T inv(M_L)^T    trsm_kernel with inv(M_L)
+//   trailing update A22 -= L21 U12 over the whole square: lower part into F, upper part into FU (lu_update_kernel)
+// After the numeric phase the L side (F, inv(M_L)) and the U side (FU, inv(U)^T) each get T, M21 and the sweep copies
+// from the existing kernels: the forward sweep reads the L side, the backward sweep the U side, as it reads L^T.
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+// one workgroup per active front: LU of the W x W diagonal block (row interchanges inside it), inv(M_L) -> InvL,
+// inv(U)^T -> InvU.  Static pivots as on the Bunch-Kaufman path (flag[2]); flag[3] counts the row interchanges.
+__global__ __launch_bounds__(kThreads) void lu_inv_kernel(FrontArrays fa, const int* __restrict__ fronts, int step,
+                                                         const double* __restrict__ F, const double* __restrict__ FU,
+                                                         double* __restrict__ InvL, double* __restrict__ InvU,
+                                                         int* __restrict__ flag) {
+  __shared__ double A[TW * TLD];  // the block, column-major A[j * TLD + i]; after step k: L below, U on and above the diagonal
+  __shared__ double X[TW * TLD];  // lane c's column of inv(M_L), then of inv(U)
+  __shared__ int perm[TW];        // row i of P A11 is row perm[i] of A11
+  __shared__ int s_kp, s_bad;
+  const int f = fronts[blockIdx.x];
+  const int W = fa.W;
+  const int ns = fa.ns[f];
+  const int64_t d = ns + fa.bs[f];
+  const int j0 = step * W;
+  const int w = min(W, ns - j0);
+  const int64_t o = fa.foff[f] + static_cast<int64_t>(j0) * d + j0;
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < w * w; idx += kThreads) {
+    const int j = idx / w, i = idx - j * w;
+    A[j * TLD + i] = (i >= j) ? F[o + static_cast<int64_t>(j) * d + i] : FU[o + static_cast<int64_t>(i) * d + j];
+  }
+  if (tid < w) perm[tid] = tid;
+  if (tid == 0) s_bad = 0;
+  __syncthreads();
+  for (int k = 0; k < w; ++k) {
+    if (tid == 0) {  // pivot: the largest candidate of column k inside the panel block
+      int kp = k;
+      double big = fabs(A[k * TLD + k]);
+      for (int i = k + 1; i < w; ++i) {
+        const double v = fabs(A[k * TLD + i]);
+        if (v > big) { big = v; kp = i; }
+      }
+      if (!(big >= 0.0) || !(big < 1.0e300)) {
+        s_bad = 1;  // not finite
+      } else if (big <= fa.pivtol) {
+        kp = k;  // no usable pivot in this column of the panel block: static pivot
+        A[k * TLD + k] = (A[k * TLD + k] < 0.0) ? -fa.pivtol : fa.pivtol;
+        atomicAdd(flag + 2, 1);
+        if (!(fa.pivtol > 0.0)) s_bad = 1;  // (all-zero matrix)
+      }
+      if (kp != k) atomicAdd(flag + 3, 1);
+      s_kp = kp;
+    }
+    __syncthreads();
+    if (s_bad) break;
+    const int kp = s_kp;
+    if (kp != k) {  // whole rows of the block (the multipliers of earlier columns included)
+      for (int j = tid; j < w; j += kThreads) {
+        const double t = A[j * TLD + k];
+        A[j * TLD + k] = A[j * TLD + kp];
+        A[j * TLD + kp] = t;
+      }
+      if (tid == 0) {
+        const int t = perm[k];
+        perm[k] = perm[kp];
+        perm[kp] = t;
+      }
+      __syncthreads();
+    }
+    const double piv = A[k * TLD + k];
+    for (int i = k + 1 + tid; i < w; i += kThreads) A[k * TLD + i] /= piv;
+    __syncthreads();
+    const int m = w - k - 1;
+    for (int idx = tid; idx < m * m; idx += kThreads) {
+      const int cc = idx / m, ii = idx - cc * m;
+      A[(k + 1 + cc) * TLD + k + 1 + ii] -= A[k * TLD + k + 1 + ii] * A[(k + 1 + cc) * TLD + k];
+    }
+    __syncthreads();
+  }
+  if (s_bad) {
+    if (tid == 0) atomicCAS(flag, 0, f + 1);
+    // leave something finite behind: the caller reports the failure, later launches of this numeric phase must not fault
+    for (int idx = tid; idx < w * w; idx += kThreads) {
+      const int j = idx / w, i = idx - j * w;
+      A[j * TLD + i] = (i == j) ? 1.0 : 0.0;
+    }
+    if (tid < w) perm[tid] = tid;
+    __syncthreads();
+  }
+  if (tid < w) fa.sgn[fa.c0[f] + j0 + tid] = 1.0;
+  double* Il = InvL + fa.ioff[f] + static_cast<int64_t>(step) * W * W;
+  double* Iu = InvU + fa.ioff[f] + static_cast<int64_t>(step) * W * W;
+  if (tid < w) {
+    const int c = tid;
+    double* x = X + c * TLD;
+    // inv(M_L) e_c = inv(L) P e_c: forward substitution with the unit lower L
+    for (int i = 0; i < w; ++i) {
+      double sum = (perm[i] == c) ? 1.0 : 0.0;
+      for (int j = 0; j < i; ++j) sum -= A[j * TLD + i] * x[j];
+      x[i] = sum;
+    }
+    for (int i = 0; i < w; ++i) Il[c * W + i] = x[i];
+    // inv(U) e_c: back substitution; stored as row c of inv(U)^T
+    for (int i = c; i >= 0; --i) {
+      double sum = (i == c) ? 1.0 : 0.0;
+      for (int j = i + 1; j <= c; ++j) sum -= A[j * TLD + i] * x[j];
+      x[i] = sum / A[i * TLD + i];
+    }
+    for (int i = 0; i < w; ++i) Iu[i * W + c] = (i <= c) ? x[i] : 0.0;
+  }
+}
+
+// trailing update of both triangles, A22 -= L21 U12, one 64 x 64 tile per workgroup over the whole trailing square:
+// workgroup (ti, tj) with ti >= tj updates tile (ti, tj) of F, with ti <= tj tile (tj, ti) of FU (diagonal: both).
+// G(p, q) -= sum_k X(p, k) Y(q, k) with (G, X, Y) = (F, F, FU) or (FU, FU, F), panel columns k; fp64 MFMA
+// (v_mfma_f64_16x16x4: D(q, p) with p = lane & 15 along the column-major rows of G -- coalesced stores)
+__global__ __launch_bounds__(kThreads) void lu_update_kernel(FrontArrays fa, const int* __restrict__ fronts, int na, int step,
+                                                            const int* __restrict__ pref_chunks,
+                                                            const int* __restrict__ pref_tiles, double* __restrict__ F,
+                                                            double* __restrict__ FU) {
+  const int q = find_slot(pref_tiles, na, blockIdx.x);
+  const int nch = pref_chunks[q + 1] - pref_chunks[q];
+  const int local = blockIdx.x - pref_tiles[q];
+  const int ti = local / nch, tj = local - ti * nch;
+  __shared__ double Xs[TW * TLD];
+  __shared__ double Ys[TW * TLD];
+  const int f = fronts[q];
+  const int W = fa.W;
+  const int ns = fa.ns[f];
+  const int64_t d = ns + fa.bs[f];
+  const int j0 = step * W;
+  const int w = min(W, ns - j0);
+  const int j1 = j0 + w;
+  const int64_t fo = fa.foff[f];
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+  const int kd = (w + 3) & ~3;
+  auto tile = [&](double* G, const double* Xg, const double* Yg, int P0, int Q0, bool strict) {
+    const int rows_p = min(TW, static_cast<int>(d) - P0), rows_q = min(TW, static_cast<int>(d) - Q0);
+    const double* Xp = Xg + fo + static_cast<int64_t>(j0) * d;  // panel columns
+    const double* Yp = Yg + fo + static_cast<int64_t>(j0) * d;
+    for (int idx = tid; idx < TW * TW; idx += kThreads) {
+      const int k = idx / TW, r = idx - k * TW;
+      Xs[k * TLD + r] = (k < w && r < rows_p) ? Xp[static_cast<int64_t>(k) * d + P0 + r] : 0.0;
+      Ys[k * TLD + r] = (k < w && r < rows_q) ? Yp[static_cast<int64_t>(k) * d + Q0 + r] : 0.0;
+    }
+    __syncthreads();
+    double4_t c[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) c[n] = double4_t{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < kd; k0 += 4) {
+      const int k = k0 + lk;
+      const double a = Ys[k * TLD + 16 * wave + li];  // A operand: Y(q = 16 wave + (lane & 15), k)
+#pragma unroll
+      for (int n = 0; n < 4; ++n)                     // B operand: X(p = 16 n + (lane & 15), k)
+        c[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Xs[k * TLD + 16 * n + li], c[n], 0, 0, 0);
+    }
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int p = 16 * n + li, qq = 16 * wave + lk + 4 * r;  // D(row qq, col p)
+        const int gp = P0 + p, gq = Q0 + qq;
+        if (p < rows_p && qq < rows_q && (strict ? gp > gq : gp >= gq)) G[fo + static_cast<int64_t>(gq) * d + gp] -= c[n][r];
+      }
+    __syncthreads();
+  };
+  if (ti >= tj) tile(F, F, FU, j1 + ti * TW, j1 + tj * TW, false);
+  if (ti <= tj) tile(FU, FU, F, j1 + tj * TW, j1 + ti * TW, true);
+}
+
 
 // ------------------------------------------------------------------ explicit inverses
 // The sweeps never substitute: after the numeric factorisation every front's triangle is inverted,
@@ -671,7 +858,6 @@ __global__ __launch_bounds__(kThreads) void m21_kernel(FrontArrays fa, const int
 //    column tiles; per K-step of 4 a lane feeds ONE double of A and one of B per tile, so the LDS
 //    traffic per flop is ~9x lower than the vector form (which is LDS-bound at KB = 32).  Result map of
 //    the f64 MFMA: acc[reg] <-> (row = (lane>>4) + 4*reg, col = lane&15) inside the 16 x 16 tile.
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 template <int KPT>
 struct Tile {
@@ -2046,6 +2232,11 @@ constexpr char overflow_sum_kernel_family[] = "overflow_sum_kernel";
 struct SweepLaunch {
   int variant, level, kb;
 };
+// the factor arrays of one solve: [T; M21] in place (F, T) and its copies, per direction
+struct SweepCopies {
+  const double *fF, *fT, *Fb, *Fm;  // forward
+  const double *bF, *bT, *Ft, *Bm;  // backward
+};
 struct SweepRecord {
   std::vector<SweepLaunch> launches;  // of the most recent solve
 };
@@ -2116,6 +2307,27 @@ struct eigd_factor {
   int64_t data_len = 0;
   bool record_sweeps = false;  // solves of the factor and of its lanes record their launches (tests)
   SweepRecord rec;             // ... those of the factor's own stream
+  // LU factor of an unsymmetric matrix (eigd_factor_create_lu): the U side has buffers of its own -- the transposed
+  // upper triangles FU, inv(U)^T per panel, T and the copies the backward sweep reads; the L side uses the ones above
+  bool lu = false;
+  double *d_FU = nullptr, *d_InvU = nullptr, *d_TU = nullptr, *d_FtU = nullptr, *d_BmU = nullptr;
+  int64_t *d_u_src = nullptr, *d_u_dst = nullptr;  // scatter of the strictly upper entries into FU
+  int64_t nupper = 0;
+  int n_interchanges = 0;  // row interchanges of the LU panels
+
+  // the arrays the sweeps read: forward from the L side, backward from the U side (the same ones for L S L^T)
+  SweepCopies copies() const {
+    SweepCopies c;
+    c.fF = d_F;
+    c.fT = d_T;
+    c.Fb = d_Fb;
+    c.Fm = d_Fm;
+    c.bF = lu ? d_FU : d_F;
+    c.bT = lu ? d_TU : d_T;
+    c.Ft = lu ? d_FtU : d_Ft;
+    c.Bm = lu ? d_BmU : d_Bm;
+    return c;
+  }
 
   FrontArrays fa() const {
     FrontArrays a;
@@ -2155,7 +2367,120 @@ int upload(eigd_factor* f, T** dptr, const std::vector<T>& h) {
   return EIGD_OK;
 }
 
+// sqrt(eps) * max |a_ij| of the values on the device: the threshold of the static pivots
+int static_pivot_tolerance(eigd_factor* f, hipStream_t st) {
+  constexpr int nbm = 512;
+  hipLaunchKernelGGL(absmax_kernel, dim3(nbm), dim3(kThreads), 0, st, f->data_len, f->d_data, f->d_red);
+  EIGD_LAUNCH_CHECK();
+  double part[nbm];
+  EIGD_HIP(hipMemcpyAsync(part, f->d_red, sizeof(part), hipMemcpyDeviceToHost, st));
+  EIGD_HIP(hipStreamSynchronize(st));
+  double amax = 0.0;
+  for (double v : part) amax = std::max(amax, v);
+  f->pivtol = 1.4901161193847656e-08 * amax;
+  return EIGD_OK;
+}
+
+// numeric phase of an LU factor (see lu_inv_kernel): the same level and panel schedule as the symmetric one, every
+// step on both triangles
+int numeric_lu(eigd_factor* f, const double* data, bool on_device) {
+  const Symbolic& s = *f->sym;
+  hipStream_t st = f->ctx->stream;
+  f->pivoted = true;  // dense diagonal blocks of T on the L side
+  EIGD_HIP(hipMemcpyAsync(f->d_data, data, sizeof(double) * f->data_len,
+                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  EIGD_HIP(hipMemsetAsync(f->d_F, 0, sizeof(double) * s.front_doubles, st));
+  EIGD_HIP(hipMemsetAsync(f->d_FU, 0, sizeof(double) * s.front_doubles, st));
+  EIGD_HIP(hipMemsetAsync(f->d_flag, 0, 4 * sizeof(int), st));
+  int rc = static_pivot_tolerance(f, st);
+  if (rc != EIGD_OK) return rc;
+  {
+    const int nb = static_cast<int>(std::min<int64_t>((s.nlower + 255) / 256, 65536));
+    hipLaunchKernelGGL(scatter_a_kernel, dim3(std::max(nb, 1)), dim3(256), 0, st, s.nlower, f->d_a_src, f->d_a_dst,
+                       f->d_data, f->d_F);
+    EIGD_LAUNCH_CHECK();
+    const int nbu = static_cast<int>(std::min<int64_t>((f->nupper + 255) / 256, 65536));
+    hipLaunchKernelGGL(scatter_a_kernel, dim3(std::max(nbu, 1)), dim3(256), 0, st, f->nupper, f->d_u_src, f->d_u_dst,
+                       f->d_data, f->d_FU);
+    EIGD_LAUNCH_CHECK();
+  }
+  const FrontArrays fa = f->fa();
+  for (int l = 0; l < s.nlevels; ++l) {
+    for (int slot = 0; slot < s.maxslots; ++slot) {  // contribution blocks: both triangles
+      const size_t rec = static_cast<size_t>(l) * s.maxslots + slot;
+      const int cnt = s.cs_ptr[rec + 1] - s.cs_ptr[rec];
+      if (cnt == 0) continue;
+      for (double* G : {f->d_F, f->d_FU}) {
+        hipLaunchKernelGGL(extend_add_kernel, dim3(cnt, f->ea_split[rec]), dim3(kThreads), 0, st, fa,
+                           f->d_cs_child + s.cs_ptr[rec], G);
+        EIGD_LAUNCH_CHECK();
+      }
+    }
+    const int* fronts = f->d_lvl_fronts + s.lvl_ptr[l];
+    for (int step = 0; step < s.lvl_nsteps[l]; ++step) {
+      const int rec = s.ls_ptr[l] + step;
+      const int na = s.ls_nactive[rec];
+      const int64_t po = s.ls_pref_ptr[rec];
+      const int nchunks = s.pref_chunks[po + na];
+      const int ntiles = s.pref_tiles[po + na];
+      hipLaunchKernelGGL(lu_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->d_F, f->d_FU, f->d_Inv,
+                         f->d_InvU, f->d_flag);
+      EIGD_LAUNCH_CHECK();
+      if (nchunks > 0) {
+        hipLaunchKernelGGL(trsm_kernel, dim3(nchunks), dim3(kThreads), 0, st, fa, fronts, na, step,
+                           f->d_pref_chunks + po, f->d_F, f->d_InvU);  // L21 = A21 inv(U)
+        EIGD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(trsm_kernel, dim3(nchunks), dim3(kThreads), 0, st, fa, fronts, na, step,
+                           f->d_pref_chunks + po, f->d_FU, f->d_Inv);  // U12^T = A12^T inv(M_L)^T
+        EIGD_LAUNCH_CHECK();
+        hipLaunchKernelGGL(lu_update_kernel, dim3(ntiles), dim3(kThreads), 0, st, fa, fronts, na, step,
+                           f->d_pref_chunks + po, f->d_pref_tiles + po, f->d_F, f->d_FU);
+        EIGD_LAUNCH_CHECK();
+      }
+    }
+  }
+  // T and M21 of both sides; then the copies.  The copy kernels write the forward and the backward copies together:
+  // the U side goes first, and what it leaves in the forward copies (Fb, Fm) the L side overwrites entry for entry;
+  // the L side's backward copies land in Ft / Bm, which an LU factor's sweeps do not read
+  struct Side { double *F, *Inv, *T, *Ft, *Bm; };
+  const Side sides[2] = {{f->d_FU, f->d_InvU, f->d_TU, f->d_FtU, f->d_BmU}, {f->d_F, f->d_Inv, f->d_T, f->d_Ft, f->d_Bm}};
+  for (const Side& sd : sides) {
+    if (f->n_tri > 0) {
+      hipLaunchKernelGGL(trinv_kernel, dim3(f->n_tri), dim3(kThreads), 0, st, fa, f->d_tri_pref, s.nfronts, sd.F, sd.Inv,
+                         sd.T);
+      EIGD_LAUNCH_CHECK();
+    }
+    if (f->n_m21 > 0) {
+      hipLaunchKernelGGL(m21_kernel, dim3(f->n_m21), dim3(kThreads), 0, st, fa, f->d_m_pref, s.nfronts, sd.F, sd.T);
+      EIGD_LAUNCH_CHECK();
+    }
+    if (f->n_tr > 0) {
+      hipLaunchKernelGGL(transpose_front_kernel, dim3(f->n_tr), dim3(kThreads), 0, st, fa, f->d_tr_pref, s.nfronts,
+                         f->d_ftoff, sd.F, sd.T, sd.Ft, f->d_Fb);
+      EIGD_LAUNCH_CHECK();
+    }
+    if (f->n_mt > 0) {
+      hipLaunchKernelGGL(pack_frag_kernel, dim3(f->n_mt), dim3(kThreads), 0, st, fa, f->d_ff, f->d_mt_pref, f->n_ff, sd.F,
+                         sd.T, f->d_Fm, sd.Bm);
+      EIGD_LAUNCH_CHECK();
+    }
+  }
+  int flag[4] = {0, 0, 0, 0};
+  EIGD_HIP(hipMemcpyAsync(flag, f->d_flag, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  EIGD_HIP(hipStreamSynchronize(st));
+  f->n_negative = 0;
+  f->n_perturbed = flag[2];
+  f->n_interchanges = flag[3];
+  if (flag[0] != 0) {
+    set_error("non-finite entries in front %d: the matrix is singular to working precision or holds inf / NaN",
+              flag[0] - 1);
+    return EIGD_E_NOTSPD;
+  }
+  return EIGD_OK;
+}
+
 int numeric(eigd_factor* f, const double* data, bool on_device = false, bool pivot = false) {
+  if (f->lu) return numeric_lu(f, data, on_device);
   const Symbolic& s = *f->sym;
   hipStream_t st = f->ctx->stream;
   f->pivoted = pivot;
@@ -2233,15 +2558,8 @@ int numeric(eigd_factor* f, const double* data, bool on_device = false, bool piv
   // examples never come here and keep the plain (bitwise unchanged) Cholesky path.
   if (!pivot && (flag[0] != 0 || flag[1] != 0)) {
     // the threshold of the static pivots: sqrt(eps) * max |a_ij| (the values are on the device: reduced there)
-    constexpr int nbm = 512;
-    hipLaunchKernelGGL(absmax_kernel, dim3(nbm), dim3(kThreads), 0, st, f->data_len, f->d_data, f->d_red);
-    EIGD_LAUNCH_CHECK();
-    double part[nbm];
-    EIGD_HIP(hipMemcpyAsync(part, f->d_red, sizeof(part), hipMemcpyDeviceToHost, st));
-    EIGD_HIP(hipStreamSynchronize(st));
-    double amax = 0.0;
-    for (double v : part) amax = std::max(amax, v);
-    f->pivtol = 1.4901161193847656e-08 * amax;
+    const int rc = static_pivot_tolerance(f, st);
+    if (rc != EIGD_OK) return rc;
     return numeric(f, nullptr, true, true);
   }
   if (flag[0] != 0) {
@@ -2276,8 +2594,8 @@ constexpr int kWaveMaxKpt = 2;   // widest sweep (units of 4 columns) whose sing
   } while (0)
 
 template <int KPT>
-int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, int* wT, const double* dIn, int ldin,
-          double* dX, int ldx, int kb, double alpha, SweepRecord* rec) {
+int sweep(eigd_factor* f, const SweepCopies& cp, hipStream_t st, double* wV, double* wY, double* wP, int* wT,
+          const double* dIn, int ldin, double* dX, int ldx, int kb, double alpha, SweepRecord* rec) {
   const Symbolic& s = *f->sym;
   const FrontArrays fa = f->fa();
   // every sweep width (KB = 4, 8, 16, 32 columns) has its own set of carry planes: rows are KB wide and the
@@ -2307,8 +2625,8 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
   // fronts with several column tiles, MFMA widths: matrix operands straight from the fragment-major copies (only the
   // vector block in LDS); the vector-FMA widths stage the column-major panels through LDS
   const unsigned lds_frag = static_cast<unsigned>(sizeof(double) * (TW + 1) * Tile<KPT>::BLD);
-  const double* sF = f->d_F;  // the panels [T; M21] in place (F and T)
-  const double* sT = f->d_T;
+  const double* sF = cp.fF;  // the panels [T; M21] in place (F and T), forward side
+  const double* sT = cp.fT;
   // raw buffer accesses take 32-bit byte offsets: a carry plane and the caller's block must stay below 4 GB, else the
   // single-tile fronts of the MFMA widths go through the tile kernels
   const bool thin_buf = f->v_rows * static_cast<int64_t>(KB) * 8 <= kBufMax && static_cast<int64_t>(s.n) * ldin * 8 <= kBufMax;
@@ -2352,10 +2670,10 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
   do {                                                                                                                   \
     if (fa.tri)                                                                                                          \
       EIGD_SWEEP_LAUNCH(fwd_thin_kernel, (KB, NKS, NSLV, WPFV, true), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
-                         alpha, wV, wY, kb, f->d_Fb);                                                                    \
+                         alpha, wV, wY, kb, cp.Fb);                                                                    \
     else                                                                                                                 \
       EIGD_SWEEP_LAUNCH(fwd_thin_kernel, (KB, NKS, NSLV, WPFV, false), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
-                         alpha, wV, wY, kb, f->d_Fb);                                                                    \
+                         alpha, wV, wY, kb, cp.Fb);                                                                    \
   } while (0)
         if (!leaf && two && nks >= 12) {
           // fronts of 33 to 64 own columns with carry planes: as many waves per front as give the level >= 2048 waves
@@ -2426,19 +2744,19 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
             EIGD_SWEEP_LAUNCH(v1_assemble_kernel, (KPT, 2), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin, alpha, wV,
                                wV1, kb);
             EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, true, true), multi_grid(nwg - nsingle), dim3(kThreads),
-                               lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
+                               lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
           } else {
             EIGD_SWEEP_LAUNCH(v1_assemble_kernel, (KPT, kMaxS + 1), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin,
                                alpha, wV, wV1, kb);
             EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, true, true), multi_grid(nwg - nsingle),
-                               dim3(kThreads), lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
+                               dim3(kThreads), lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
           }
         } else if (two)
           EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, true, false), multi_grid(nwg - nsingle), dim3(kThreads),
-                             lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
+                             lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
         else
           EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, true, false), multi_grid(nwg - nsingle),
-                             dim3(kThreads), lds_frag, st, fa, la, f->d_Fm, sT, dIn, ldin, alpha, wV, wY);
+                             dim3(kThreads), lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
       } else {
         if (two)
           EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, false, false), multi_grid(nwg - nsingle), dim3(kThreads),
@@ -2464,19 +2782,19 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
       if constexpr (Tile<KPT>::kMfma) {
         if (KPT >= 8 && f->h_bwd_mxbs[l] <= kLidxMax)
           EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, true, (KPT >= 8)), multi_grid(nwg - nsb), dim3(kThreads),
-                             lds_frag + 4u * static_cast<unsigned>((f->h_bwd_mxbs[l] + 3) & ~3), st, fa, la, sF, sT, f->d_Bm,
+                             lds_frag + 4u * static_cast<unsigned>((f->h_bwd_mxbs[l] + 3) & ~3), st, fa, la, cp.bF, cp.bT, cp.Bm,
                              wY, dX, ldx);
         else
           EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, true, false), multi_grid(nwg - nsb), dim3(kThreads), lds_frag, st, fa,
-                             la, sF, sT, f->d_Bm, wY, dX, ldx);
+                             la, cp.bF, cp.bT, cp.Bm, wY, dX, ldx);
       }
       else
-        EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, false, false), multi_grid(nwg - nsb), dim3(kThreads), lds_bytes(TW), st, fa, la, sF,
-                           sT, f->d_Ft, wY, dX, ldx);
+        EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, false, false), multi_grid(nwg - nsb), dim3(kThreads), lds_bytes(TW), st, fa, la, cp.bF,
+                           cp.bT, cp.Ft, wY, dX, ldx);
       EIGD_LAUNCH_CHECK();
     }
     if (narrow) {
-      EIGD_SWEEP_LAUNCH(bwd_wave_kernel, (KB), dim3(nwave), dim3(64), 0, st, fa, f->d_wave_wg + f->h_wave_ptr[l], f->d_Ft,
+      EIGD_SWEEP_LAUNCH(bwd_wave_kernel, (KB), dim3(nwave), dim3(64), 0, st, fa, f->d_wave_wg + f->h_wave_ptr[l], cp.Ft,
                          wY, dX, ldx, kb);
       EIGD_LAUNCH_CHECK();
     } else if (thin) {
@@ -2486,10 +2804,10 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
 #define EIGD_THIN_BWD(NOB, CHV)                                                                                   \
   do {                                                                                                            \
     if (fa.tri)                                                                                                   \
-      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, true), dim3(nwave), dim3(64), 0, st, fa, recs, f->d_Ft, wY, \
+      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, true), dim3(nwave), dim3(64), 0, st, fa, recs, cp.Ft, wY, \
                          dX, ldx, kb);                                                                            \
     else                                                                                                          \
-      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, false), dim3(nwave), dim3(64), 0, st, fa, recs, f->d_Ft, \
+      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, false), dim3(nwave), dim3(64), 0, st, fa, recs, cp.Ft, \
                          wY, dX, ldx, kb);                                                                        \
   } while (0)
         if (nks == 4)
@@ -2503,7 +2821,7 @@ int sweep(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, in
       }
     } else if (nsb > 0) {  // single-column-tile fronts: LDS tiles as tall as the level needs
       EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, true, false, false), dim3(nsb), dim3(kThreads), lds_bytes(f->h_bwd_kd[l]), st, fa,
-                         level_args(f->d_bwd_wg + f->h_bwd_ptr[l], f->h_bwd_kd[l]), sF, sT, f->d_Ft, wY, dX, ldx);
+                         level_args(f->d_bwd_wg + f->h_bwd_ptr[l], f->h_bwd_kd[l]), cp.bF, cp.bT, cp.Ft, wY, dX, ldx);
       EIGD_LAUNCH_CHECK();
     }
   }
@@ -2599,6 +2917,14 @@ int eigd_symbolic_get_i64(eigd_symbolic* h, const char* name, int64_t* out, int6
   EIGD_GET("f_ioff", s.f_ioff)
   EIGD_GET("a_src", s.a_src)
   EIGD_GET("a_dst", s.a_dst)
+  if (std::strcmp(name, "u_src") == 0 || std::strcmp(name, "u_dst") == 0) {  // (built on demand)
+    if (!ensure_upper_map(h)) {
+      set_error("upper scatter map: %s", s.error.c_str());
+      return EIGD_E_INVALID;
+    }
+    EIGD_GET("u_src", s.u_src)
+    EIGD_GET("u_dst", s.u_dst)
+  }
   set_error("unknown int64 symbolic array '%s'", name);
   return EIGD_E_INVALID;
 }
@@ -2614,16 +2940,22 @@ int eigd_factor_free(eigd_factor* f) {
                   f->d_bwd_wg,    f->d_tri_pref,    f->d_m_pref,     f->d_ov_dst,   f->d_ov_ptr, f->d_ov_src,
                   f->d_toff,      f->d_T,           f->d_sgn,        f->d_aux,      f->d_bout,  f->d_tickets,
                   f->d_P,         f->d_wave_wg,     f->d_ftoff,      f->d_tr_pref,  f->d_Ft,  f->d_Fb,
-                  f->d_Fm,        f->d_Bm,          f->d_ff,         f->d_mt_pref,  f->d_red,   f->d_pre_wg};
+                  f->d_Fm,        f->d_Bm,          f->d_ff,         f->d_mt_pref,  f->d_red,   f->d_pre_wg,
+                  f->d_FU,        f->d_InvU,        f->d_TU,         f->d_FtU,      f->d_BmU,   f->d_u_src,
+                  f->d_u_dst};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete f;
   return EIGD_OK;
 }
 
-int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eigd_factor** out) {
+static int create_factor(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eigd_factor** out, bool lu) {
   EIGD_REQUIRE(ctx && h && hdata && out, "null argument");
   *out = nullptr;
+  if (lu && !ensure_upper_map(h)) {
+    set_error("upper scatter map: %s", h->s.error.c_str());
+    return EIGD_E_INVALID;
+  }
   const Symbolic& s = h->s;
   EIGD_HIP(hipSetDevice(ctx->device));
   // ---- host tables of the sweeps
@@ -2985,6 +3317,19 @@ int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eig
   UP(d_a_src, s.a_src)
   UP(d_a_dst, s.a_dst)
   UP(d_v_src, s.v_src)
+  if (lu) {
+    // FU holds the upper triangle transposed: an upper entry goes to the mirror of its place in the front square
+    std::vector<int64_t> fu_dst(s.u_dst.size());
+    for (size_t e = 0; e < s.u_dst.size(); ++e) {
+      const int64_t dst = s.u_dst[e];
+      const int q = static_cast<int>(std::upper_bound(s.f_foff.begin(), s.f_foff.end(), dst) - s.f_foff.begin()) - 1;
+      const int64_t dq = s.f_ns[q] + s.f_bs[q], loc = dst - s.f_foff[q];
+      fu_dst[e] = s.f_foff[q] + (loc % dq) * dq + loc / dq;
+    }
+    UP(d_u_src, s.u_src)
+    UP(d_u_dst, fu_dst)
+    f->nupper = static_cast<int64_t>(s.u_src.size());
+  }
   {
     // which carry planes hold a contribution on which row: child number q of a front writes plane q at the parent's
     // rows rel(border); the summed surplus children arrive in plane nslot - 1
@@ -3001,6 +3346,8 @@ int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eig
 #undef UP
   int64_t maxsrc = 0;
   for (int64_t e : s.a_src) maxsrc = std::max(maxsrc, e);
+  if (lu)
+    for (int64_t e : s.u_src) maxsrc = std::max(maxsrc, e);
   f->data_len = maxsrc + 1;
   // the caller's CSR data array may be longer (upper-triangle entries after the last lower one): we copy a prefix
   auto dmalloc = [&](double** p, size_t count) -> int {
@@ -3037,8 +3384,15 @@ int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eig
   rc = dmalloc(&f->d_V, static_cast<size_t>(nplanes) * v_rows * kPlaneCols);
   rc = dmalloc(&f->d_Y, static_cast<size_t>(s.sumd) * KBMAX);
   rc = dmalloc(&f->d_sgn, static_cast<size_t>(s.n));
+  if (lu) {  // the U side
+    rc = dmalloc(&f->d_FU, s.front_doubles);
+    rc = dmalloc(&f->d_InvU, s.inv_doubles);
+    rc = dmalloc(&f->d_TU, static_cast<size_t>(f->t_doubles));
+    rc = dmalloc(&f->d_FtU, static_cast<size_t>(f->ft_doubles));
+    rc = dmalloc(&f->d_BmU, static_cast<size_t>(std::max<int64_t>(f->bm_doubles, 1)));
+  }
   if (rc == EIGD_OK) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_flag), 3 * sizeof(int));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_flag), 4 * sizeof(int));
     if (e != hipSuccess) {
       set_error("hipMalloc failed: %s", hipGetErrorString(e));
       rc = EIGD_E_HIP;
@@ -3058,6 +3412,11 @@ int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eig
   }
   EIGD_HIP(hipMemsetAsync(f->d_Inv, 0, sizeof(double) * std::max<int64_t>(s.inv_doubles, 1), ctx->stream));
   EIGD_HIP(hipMemsetAsync(f->d_T, 0, sizeof(double) * std::max<int64_t>(f->t_doubles, 1), ctx->stream));  // upper triangles stay zero
+  if (lu) {
+    EIGD_HIP(hipMemsetAsync(f->d_InvU, 0, sizeof(double) * std::max<int64_t>(s.inv_doubles, 1), ctx->stream));
+    EIGD_HIP(hipMemsetAsync(f->d_TU, 0, sizeof(double) * std::max<int64_t>(f->t_doubles, 1), ctx->stream));
+  }
+  f->lu = lu;
   // carry planes: entries no child writes must read as zero, in every sweep
   EIGD_HIP(hipMemsetAsync(f->d_V, 0, sizeof(double) * std::max<int64_t>(static_cast<int64_t>(nplanes) * v_rows * kPlaneCols, 1),
                           ctx->stream));
@@ -3074,6 +3433,15 @@ int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eig
   }
   *out = f;
   return EIGD_OK;
+}
+
+int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eigd_factor** out) {
+  return create_factor(ctx, h, hdata, out, false);
+}
+
+// lu = splu(mat) (reference 11-17) for any square matrix on the symbolic's (symmetrised) pattern
+int eigd_factor_create_lu(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, eigd_factor** out) {
+  return create_factor(ctx, h, hdata, out, true);
 }
 
 int eigd_factor_refactor(eigd_factor* f, const double* hdata) {
@@ -3096,16 +3464,17 @@ static int solve_blocks(eigd_factor* f, hipStream_t st, double* wV, double* wY, 
   EIGD_REQUIRE(k >= 1 && ldin >= k && ldout >= k, "bad block shape k=%d ldin=%d ldout=%d", k, ldin, ldout);
   SweepRecord* rec = f->record_sweeps ? &record : nullptr;
   if (rec) rec->launches.clear();
+  const SweepCopies cp = f->copies();
   for (int c0 = 0; c0 < k; c0 += KBMAX) {
     const int kb = std::min(KBMAX, k - c0);
     int rc;
     // 5 to 8 columns go through the 16-column kernels, whose single-tile levels are MFMA wave kernels (1.26 -> 1.09 ms)
     if (kb <= 4)
-      rc = sweep<1>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+      rc = sweep<1>(f, cp, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     else if (kb <= 16)
-      rc = sweep<4>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+      rc = sweep<4>(f, cp, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     else
-      rc = sweep<8>(f, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+      rc = sweep<8>(f, cp, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     if (rc != EIGD_OK) return rc;
   }
   return EIGD_OK;
@@ -3196,10 +3565,11 @@ int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int*
 
 int eigd_factor_stats(eigd_factor* f, double* out, int nout) {
   EIGD_REQUIRE(f && out && nout >= 1, "null argument");
-  const double v[7] = {static_cast<double>(f->sym->nnzL), static_cast<double>(f->bytes), f->sym->flops,
+  const double v[9] = {static_cast<double>(f->sym->nnzL), static_cast<double>(f->bytes), f->sym->flops,
                        static_cast<double>(f->sym->nfronts), static_cast<double>(f->n_negative),
-                       static_cast<double>(f->n_perturbed), static_cast<double>(f->nplanes)};
-  for (int i = 0; i < nout && i < 7; ++i) out[i] = v[i];
+                       static_cast<double>(f->n_perturbed), static_cast<double>(f->nplanes),
+                       f->lu ? 1.0 : 0.0, static_cast<double>(f->n_interchanges)};
+  for (int i = 0; i < nout && i < 9; ++i) out[i] = v[i];
   return EIGD_OK;
 }
 

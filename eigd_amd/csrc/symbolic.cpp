@@ -715,10 +715,65 @@ bool analyze(int n, const int32_t* ip, const int32_t* ix, int leaf_size, int pan
     }
   }
   s.nlower = static_cast<int64_t>(s.a_src.size());
+  s.nnz = ip[n];
 
   s.v_src.assign(s.sumd, -1);
   for (int f = 0; f < nn; ++f)
     for (int r = 0; r < s.f_ns[f]; ++r) s.v_src[s.f_voff[f] + r] = s.perm[s.f_c0[f] + r];
+  return true;
+}
+
+bool build_upper_map(Symbolic& s) {
+  if (s.has_upper) return true;
+  const int n = s.n;
+  const int nf = s.nfronts;
+  // every lower entry (original row r, column c, CSR index e) from its place in the fronts; on a structurally symmetric
+  // pattern the strictly upper entries are exactly the mirrors (c, r) of the off-diagonal ones
+  struct Up { int row, col; int64_t dst; };
+  std::vector<Up> up;
+  up.reserve(static_cast<size_t>(std::max<int64_t>(s.nnz - s.nlower, 0)));
+  std::vector<int64_t> cnt(static_cast<size_t>(n) + 1, 0);  // entries per original row
+  std::vector<int64_t> lower_lo(static_cast<size_t>(n), INT64_MAX), lower_hi(static_cast<size_t>(n), -1);
+  for (int64_t k = 0; k < s.nlower; ++k) {
+    const int64_t dst = s.a_dst[k], e = s.a_src[k];
+    const int f = static_cast<int>(std::upper_bound(s.f_foff.begin(), s.f_foff.begin() + nf, dst) - s.f_foff.begin()) - 1;
+    const int64_t d = s.f_ns[f] + s.f_bs[f], loc = dst - s.f_foff[f];
+    const int64_t lr = loc % d, lc = loc / d;
+    const int ni = (lr < s.f_ns[f]) ? s.f_c0[f] + static_cast<int>(lr) : s.border[s.f_bptr[f] + lr - s.f_ns[f]];
+    const int nj = s.f_c0[f] + static_cast<int>(lc);
+    const int r = s.perm[ni], c = s.perm[nj];
+    cnt[r + 1]++;
+    lower_lo[r] = std::min(lower_lo[r], e);
+    lower_hi[r] = std::max(lower_hi[r], e);
+    if (ni != nj) {
+      up.push_back(Up{c, r, s.f_foff[f] + lr * d + lc});  // mirror of the lower place: row lc, column lr
+      cnt[c + 1]++;
+    }
+  }
+  for (int i = 0; i < n; ++i) cnt[i + 1] += cnt[i];  // = the pattern's indptr if it is structurally symmetric
+  if (cnt[n] != s.nnz) {
+    s.error = "the pattern is not structurally symmetric (pass the pattern of A + 0 A^T)";
+    return false;
+  }
+  // per row, the upper entries take the CSR places the lower ones leave free, in column order
+  std::vector<char> taken(static_cast<size_t>(s.nnz), 0);
+  for (int64_t k = 0; k < s.nlower; ++k) taken[s.a_src[k]] = 1;
+  for (int i = 0; i < n; ++i)
+    if (lower_hi[i] >= 0 && (lower_lo[i] < cnt[i] || lower_hi[i] >= cnt[i + 1])) {
+      s.error = "the pattern is not structurally symmetric (pass the pattern of A + 0 A^T)";
+      return false;
+    }
+  std::sort(up.begin(), up.end(), [](const Up& a, const Up& b) { return a.row != b.row ? a.row < b.row : a.col < b.col; });
+  s.u_src.resize(up.size());
+  s.u_dst.resize(up.size());
+  int64_t e = 0;
+  for (size_t q = 0; q < up.size(); ++q) {
+    e = std::max(e, cnt[up[q].row]);
+    while (taken[e]) ++e;
+    s.u_src[q] = e++;
+    s.u_dst[q] = up[q].dst;
+  }
+  s.has_upper = true;
   return true;
 }
 

@@ -44,7 +44,12 @@ struct Symbolic {
 
   // scatter of A (values given in the caller's CSR order) into the front buffer
   int64_t nlower = 0;
+  int64_t nnz = 0;  // entries of the analysed pattern
   std::vector<int64_t> a_src, a_dst;
+  // scatter of the strictly upper entries (LU factors only, build_upper_map): u_dst is the mirror, inside the same
+  // front, of the lower destination the transposed entry would get (own row of the entry's row, place of its column)
+  bool has_upper = false;
+  std::vector<int64_t> u_src, u_dst;
   // source row (original numbering) of every front-vector row, -1 for border rows
   std::vector<int> v_src;
 
@@ -61,5 +66,9 @@ struct Symbolic {
 // dof_coords (optional, n x dim, dim <= 3): geometric nested dissection instead of level structures.
 bool analyze(int n, const int32_t* indptr, const int32_t* indices, int leaf_size, int panel_width, Symbolic& s,
              int dim = 0, const double* dof_coords = nullptr);
+
+// the upper scatter map (u_src, u_dst) of a structurally symmetric pattern (rows sorted), derived from the lower map
+// alone (the pattern itself is not kept); returns false and sets s.error when the pattern was not structurally symmetric
+bool build_upper_map(Symbolic& s);
 
 }  // namespace eigd

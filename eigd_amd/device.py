@@ -993,7 +993,7 @@ class CSRMatrix:
 
 _I32 = ("perm", "iperm", "f_c0", "f_ns", "f_bs", "f_parent", "f_level", "f_slot", "f_npanels", "border", "rel",
         "lvl_ptr", "lvl_fronts", "lvl_nsteps", "v_src")
-_I64 = ("f_bptr", "f_foff", "f_voff", "f_ioff", "a_src", "a_dst")
+_I64 = ("f_bptr", "f_foff", "f_voff", "f_ioff", "a_src", "a_dst", "u_src", "u_dst")
 
 
 class Symbolic:
@@ -1053,6 +1053,7 @@ class Symbolic:
             "perm": s["n"], "iperm": s["n"], "border": s["border_len"], "rel": s["border_len"],
             "lvl_ptr": s["nlevels"] + 1, "lvl_fronts": nf, "lvl_nsteps": s["nlevels"], "v_src": s["sumd"],
             "f_bptr": nf + 1, "a_src": s["nlower"], "a_dst": s["nlower"],
+            "u_src": self.nnz - s["nlower"], "u_dst": self.nnz - s["nlower"],
         }
         ln = lens.get(name, nf)
         if name in _I32:
@@ -1075,13 +1076,52 @@ def sweep_variants():
     return [names[i].decode() for i in range(cnt.value)]
 
 
-class Factor:
-    """Numeric LL^T factor of a symmetric positive definite CSR matrix on the device."""
+def symmetrised_pattern(A):
+    """
+    A on the pattern of A + 0 A^T with every diagonal entry stored (explicit zeros where A has none): the structurally
+    symmetric pattern an LU factor is analysed and assembled on.  Returns a canonical CSR matrix: A itself when its
+    pattern is that already.  Merges of sorted rows only (linear in nnz, no sort of the entries).
+    """
+    from scipy import sparse
 
-    def __init__(self, ctx, A, symbolic=None, leaf_size=0, panel_width=0, coords=None):
+    A = sparse.csr_matrix(A)
+    if A.dtype != np.float64:
+        A = A.astype(np.float64)
+    if not A.has_canonical_format:
+        A = A.copy()
+        A.sum_duplicates()
+    n = A.shape[0]
+    # the union of the patterns of A, A^T and the diagonal, from all-one values (sums of ones cannot cancel)
+    P = sparse.csr_matrix((np.ones(A.nnz), A.indices, A.indptr), shape=A.shape)
+    Pt = P.T.tocsr()
+    Pt.sort_indices()
+    rows = np.repeat(np.arange(n), np.diff(A.indptr))
+    if (np.array_equal(Pt.indptr, A.indptr) and np.array_equal(Pt.indices, A.indices)
+            and np.count_nonzero(rows == A.indices) == n):
+        return A  # structurally symmetric with every diagonal entry stored already
+    Q = (P + Pt + sparse.identity(n, format="csr")).tocsr()
+    Q.sort_indices()
+    # where A's entries sit in Q: Q's pattern with 2, plus 1 on A's entries
+    M = sparse.csr_matrix((np.full(Q.nnz, 2.0), Q.indices, Q.indptr), shape=A.shape) + P
+    M.sort_indices()
+    mine = M.data == 3.0
+    assert M.nnz == Q.nnz and int(np.count_nonzero(mine)) == A.nnz
+    vals = np.zeros(M.nnz)
+    vals[mine] = A.data
+    return sparse.csr_matrix((vals, M.indices, M.indptr), shape=A.shape)
+
+
+class Factor:
+    """
+    Numeric factor of a CSR matrix on the device: L S L^T of a symmetric matrix (Cholesky, Bunch-Kaufman inside the
+    panels where it is indefinite), or with ``lu=True`` LU of any square matrix (row interchanges inside the panels).
+    """
+
+    def __init__(self, ctx, A, symbolic=None, leaf_size=0, panel_width=0, coords=None, lu=False):
         from scipy import sparse
 
-        A = sparse.csr_matrix(A)
+        self.lu = bool(lu)
+        A = symmetrised_pattern(A) if self.lu else sparse.csr_matrix(A)
         if A.dtype != np.float64:
             A = A.astype(np.float64)
         A.sort_indices()
@@ -1092,7 +1132,8 @@ class Factor:
         self.symbolic = symbolic if symbolic is not None else Symbolic(A, leaf_size, panel_width, coords)
         data = np.ascontiguousarray(A.data, dtype=np.float64)
         h = c_vp()
-        call("eigd_factor_create", ctx.h, self.symbolic.h, hptr(data), C.byref(h))
+        call("eigd_factor_create_lu" if self.lu else "eigd_factor_create", ctx.h, self.symbolic.h, hptr(data),
+             C.byref(h))
         self.h = h
         if self.stats()["static_pivots"] > 0:
             self.verify_static_pivots(CSRMatrix(ctx, A))
@@ -1110,7 +1151,7 @@ class Factor:
     def refactor(self, A):
         from scipy import sparse
 
-        A = sparse.csr_matrix(A)
+        A = symmetrised_pattern(A) if self.lu else sparse.csr_matrix(A)
         A.sort_indices()
         self.symbolic.check_pattern(A)
         data = np.ascontiguousarray(A.data, dtype=np.float64)
@@ -1220,10 +1261,11 @@ class Factor:
         return lanes[key][0]
 
     def stats(self):
-        out = np.zeros(7)
-        call("eigd_factor_stats", self.h, hptr(out), 7)
+        out = np.zeros(9)
+        call("eigd_factor_stats", self.h, hptr(out), 9)
         return {"nnzL": int(out[0]), "device_bytes": int(out[1]), "flops": float(out[2]), "nfronts": int(out[3]),
-                "negative_pivots": int(out[4]), "static_pivots": int(out[5]), "workspace_planes": int(out[6])}
+                "negative_pivots": int(out[4]), "static_pivots": int(out[5]), "workspace_planes": int(out[6]),
+                "kind": "lu" if out[7] == 1 else "ldlt", "row_interchanges": int(out[8])}
 
     def solve_bytes(self, k):
         b = C.c_double()

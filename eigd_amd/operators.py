@@ -36,7 +36,8 @@ class SpLuOperator(LinearOperator):
     Shift-invert operator ``x -> mat^{-1} x`` factored and applied on the MI355X.
 
     Same surface as the reference class (``shape``, ``dtype``, ``count``, callable on
-    ``(n,)`` and ``(n, k)`` numpy arrays).  ``mat`` must be symmetric.  The factorisation is
+    ``(n,)`` and ``(n, k)`` numpy arrays).  By default ``mat`` must be symmetric (``symmetric=False``: any square
+    matrix, see below).  The factorisation is
     ``P mat P^T = L S L^T`` with ``S = diag(+-1)``: plain Cholesky for the positive definite
     shifts of the reference's examples (K - sigma M below the spectrum, K + sigma G below the
     first buckling load); for a shift inside the spectrum (the reference's CRM example, sigma = omega_0^2) the numeric
@@ -49,9 +50,16 @@ class SpLuOperator(LinearOperator):
     times against the true matrix.  A matrix that is singular to working precision as a whole is told apart by one
     refined solve of a random system at factorisation time and raises ``NotPositiveDefiniteError`` (a
     ``numpy.linalg.LinAlgError``): the shift sits on an eigenvalue.
+
+    ``symmetric=False`` factors ``P mat P^T = LL UU`` instead, for any square real (or complex-step) matrix, on the
+    pattern of ``mat + 0 mat^T``: partial pivoting (row interchanges, counted in ``row_interchanges``) inside the
+    64-column panels, static pivots as above, and every application refined once against the true matrix (three
+    times with static pivots).  An LU factor gives no inertia: ``negative_pivots`` is ``None``; ``kind`` is ``"lu"``
+    (``"ldlt"`` for the symmetric factor).
     """
 
-    def __init__(self, mat, ctx=None, symbolic=None, leaf_size=0, panel_width=0, check_symmetry=True, coords=None):
+    def __init__(self, mat, ctx=None, symbolic=None, leaf_size=0, panel_width=0, check_symmetry=True, coords=None,
+                 symmetric=True):
         if not sparse.issparse(mat):
             mat = sparse.csr_matrix(mat)
         if mat.shape[0] != mat.shape[1]:
@@ -73,15 +81,17 @@ class SpLuOperator(LinearOperator):
             mat = sparse.csr_matrix((cm.data.real.copy(), cm.indices, cm.indptr), shape=cm.shape)
         csr = mat.tocsr().astype(np.float64)  # for a symmetric matrix CSC and CSR coincide
         csr.sort_indices()
-        csr = _with_structural_diagonal(csr)
-        if check_symmetry:
+        self.symmetric = bool(symmetric)
+        if self.symmetric:  # (the LU factor symmetrises the pattern itself; the refinement applies csr as it is)
+            csr = _with_structural_diagonal(csr)
+        if check_symmetry and self.symmetric:
             x = np.random.default_rng(0).uniform(-1.0, 1.0, size=csr.shape[0])
             d = csr @ x - csr.T @ x
             if np.linalg.norm(d) > 1e-10 * max(np.linalg.norm(csr @ x), 1e-300):
-                raise ValueError("SpLuOperator (MI355X) needs a symmetric matrix")
+                raise ValueError("SpLuOperator (MI355X) needs a symmetric matrix; pass symmetric=False for an LU factor")
         # coords (optional, one row per dof): geometric nested dissection; without it the ordering is algebraic
         self.factor = Factor(self.ctx, csr, symbolic=symbolic, leaf_size=leaf_size, panel_width=panel_width,
-                             coords=coords)
+                             coords=coords, lu=not self.symmetric)
         self.symbolic = self.factor.symbolic
         self._read_inertia()
         # indefinite: pivoting is confined to the panel blocks -> one refinement step per application (three when static
@@ -89,17 +99,23 @@ class SpLuOperator(LinearOperator):
         self._mat_dev = CSRMatrix(self.ctx, csr) if self._pivoted() else None
 
     def _pivoted(self):
-        return self.negative_pivots > 0 or self.static_pivots > 0
+        # (an LU factor pivots inside its panels only: always refined)
+        return self.kind == "lu" or self.negative_pivots > 0 or self.static_pivots > 0
 
     def _read_inertia(self):
         st = self.factor.stats()
-        self.negative_pivots = st["negative_pivots"]
+        self.kind = st["kind"]
+        self.row_interchanges = st["row_interchanges"]
         self.static_pivots = st["static_pivots"]   # pivots singular inside their panel block, replaced by +-sqrt(eps)|A|
+        self._refine_steps = self.factor.STATIC_PIVOT_REFINEMENTS if self.static_pivots > 0 else 1
+        if self.kind == "lu":  # no inertia
+            self.negative_pivots = self.negative_pivots_bounds = None
+            return
+        self.negative_pivots = st["negative_pivots"]
         # a static pivot takes its sign from a diagonal entry at rounding level: the inertia is then known only up to
         # their number -- negative_pivots_bounds brackets the count of eigenvalues below the shift
         self.negative_pivots_bounds = (max(0, self.negative_pivots - self.static_pivots),
                                        self.negative_pivots + self.static_pivots)
-        self._refine_steps = self.factor.STATIC_PIVOT_REFINEMENTS if self.static_pivots > 0 else 1
 
     def _refine(self, B, X, alpha):
         """X <- X + mat^{-1} (alpha B - mat X): iterative refinement on device blocks (one step; three with static pivots)"""

@@ -443,7 +443,7 @@ class ShellBoxOnDevice:
         self._shifted.update_values_device(vS)
         self.factor.refactor_device(vS, indefinite_matrix=self._shifted)
         self.sigma = float(sigma)
-        if self.factor.static_pivots > 0:
+        if self.factor.static_pivots > 0 and self.factor.negative_pivots_bounds is not None:  # (an LU factor: no inertia)
             import warnings
 
             lo, hi = self.factor.negative_pivots_bounds

@@ -114,12 +114,20 @@ int eigd_symbolic_free(eigd_symbolic* s);
  *        [5]=sum of front dimensions [6]=max front dimension [7]=border entries [8]=lower nnz of A
  *        [9]=number of (level, step) launches [10]=flops of the numeric factorisation [11]=max columns in a front */
 int eigd_symbolic_sizes(eigd_symbolic* s, int64_t* out, int nout);
-/* copy-out of the symbolic arrays (tests emulate the numeric phase in numpy from these) */
+/* copy-out of the symbolic arrays (tests emulate the numeric phase in numpy from these); int64 "u_src" / "u_dst" (the
+ * scatter of the strictly upper entries of an LU factor: nnz - lower nnz entries each) are built on demand */
 int eigd_symbolic_get_i32(eigd_symbolic* s, const char* name, int32_t* out, int64_t cap);
 int eigd_symbolic_get_i64(eigd_symbolic* s, const char* name, int64_t* out, int64_t cap);
 
 int eigd_factor_create(eigd_ctx* ctx, eigd_symbolic* s, const double* hdata /* CSR values, full matrix */,
                        eigd_factor** out);
+/* lu = splu(mat) (reference 11-17) for a matrix that need not be symmetric: A = LL UU on the symbolic's pattern, which
+ * must be structurally symmetric (the pattern of A + 0 A^T with every diagonal entry stored); hdata = CSR values of the
+ * full matrix on that pattern.  Partial pivoting (row interchanges) inside the panel blocks, static pivots where a
+ * panel block is singular by itself.  refactor, solve, lanes, the sweep record and solve_bytes work on it as on the
+ * symmetric factor; the symbolic's upper scatter map (eigd_symbolic_get_i64 "u_src", "u_dst") is built on the
+ * first call. */
+int eigd_factor_create_lu(eigd_ctx* ctx, eigd_symbolic* s, const double* hdata, eigd_factor** out);
 int eigd_factor_refactor(eigd_factor* f, const double* hdata);
 /* the same with the CSR values already on the device (e.g. from eigd_assemble): no host round trip */
 int eigd_factor_refactor_dev(eigd_factor* f, const double* dvals);
@@ -147,7 +155,9 @@ int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int*
 /* stats: [0]=nnz(L) [1]=device bytes held [2]=flops of the numeric factorisation [3]=number of fronts
           [4]=negative pivots of P M P^T = L S L^T (inertia: eigenvalues of the pencil below the shift; 0 = SPD)
           [5]=static pivots [6]=planes of the sweeps' vector workspace (carry planes, + 1 where the right-hand sides of
-          levels with thousands of workgroups are pre-assembled) */
+          levels with thousands of workgroups are pre-assembled)
+          [7]=kind of factor (0 = L S L^T of a symmetric matrix, 1 = LU) [8]=row interchanges of the LU panels; an LU
+          factor reports 0 negative pivots (it gives no inertia) */
 int eigd_factor_stats(eigd_factor* f, double* out, int nout);
 /* bytes of L streamed by one k-column solve (algorithmic, for the roofline) */
 int eigd_factor_solve_bytes(eigd_factor* f, int k, double* bytes);
