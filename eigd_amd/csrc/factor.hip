@@ -2240,13 +2240,81 @@ struct SweepCopies {
 struct SweepRecord {
   std::vector<SweepLaunch> launches;  // of the most recent solve
 };
+// the scratch of the sweeps on one stream: the factor has one for its own stream, every lane one for another
+struct SweepWorkspace {
+  double *V = nullptr, *Y = nullptr, *P = nullptr;  // carry planes, S z, partial slabs of split chains
+  int* tickets = nullptr;                          // one per split tile, zero between sweeps
+  SweepRecord rec;                                 // launches of the most recent solve (when the factor records them)
+};
+
+// the arrays of one triangle: the fronts (the U side holds the upper triangles transposed, so every kernel but the
+// panel ones runs unchanged on either side), inv of the panels' diagonal blocks, T, the copies the backward sweep
+// reads, and the scatter of the triangle's entries of A into F
+struct FactorSide {
+  double *F = nullptr, *Inv = nullptr, *T = nullptr, *Ft = nullptr, *Bm = nullptr;
+  int64_t *src = nullptr, *dst = nullptr;
+  int64_t nmap = 0;
+};
+
+// one device array: allocated with max(count, 1) elements, then uploaded from host (count elements) or zeroed on
+// the owner's stream
+struct DeviceBuffer {
+  const char* name;
+  void** ptr;
+  size_t elem, count;
+  bool zero;
+  const void* host;  // read at creation only (cleared once uploaded)
+  size_t bytes() const { return elem * std::max<size_t>(count, 1); }
+};
+template <typename T>
+DeviceBuffer device_buffer(const char* name, T*& p, int64_t count, bool zero = false) {
+  return {name, reinterpret_cast<void**>(&p), sizeof(T), static_cast<size_t>(count), zero, nullptr};
+}
+template <typename T>
+DeviceBuffer upload_buffer(const char* name, T*& p, const std::vector<T>& h) {
+  return {name, reinterpret_cast<void**>(&p), sizeof(T), h.size(), false, h.data()};
+}
+
+// Host planning of the sweeps and of the copy kernels (plan_sweeps): what the factor keeps ...
+struct SweepTables {
+  std::vector<int> h_fwd_ptr, h_bwd_ptr;  // per level: first workgroup record
+  std::vector<int> h_thin_fwd, h_thin_bwd;  // per level: 4, 8 or 16 K-steps (of 4 own columns) of the wave-per-block kernels, 0: the tile kernels
+  std::vector<int> h_fwd_kd, h_bwd_kd;    // per level: LDS tile rows of the single-column-tile launches (multiple of 8)
+  std::vector<char> h_lvl_two;            // per level: every front has at most two children (two-plane kernels)
+  std::vector<char> h_lvl_leaf;           // per level: no front has children (kernels without carry loads)
+  std::vector<int> h_fwd_nsingle;         // per level: leading records of single-column-tile fronts (own kernel)
+  // levels whose multi-tile fronts get v1 pre-assembled (v1_assemble_kernel): one record per front and column tile
+  std::vector<int> h_pre_ptr;             // per level: first record (none: the level's workgroups gather v1 themselves)
+  bool has_v1 = false;                    // one more plane per sweep width, behind all carry planes: receives v1
+  std::vector<int> h_bwd_nsingle;         // per level: leading backward records of single-column-tile fronts
+  std::vector<int> h_bwd_mxbs;            // per level: the longest border among the fronts with several column tiles
+  // narrow sweeps (k <= 8): one record per single-tile front and level, the transposed copy of [T; M21]
+  std::vector<int> h_wave_ptr;
+  std::vector<int> ov_lvl_ptr;       // per level: range of overflow rows (extra rows of V after the sumd front rows)
+  std::vector<int> ea_split;         // per (level, slot): grid.y of the extend-add launches
+  int64_t n_slabs = 0;
+  int n_tickets = 0;
+  int nslot = 0, nplanes = 0;        // planes the parents read; planes allocated (+ scratch when there are surplus children)
+  int64_t t_doubles = 0, v_rows = 0;
+  int64_t ft_doubles = 0, fm_doubles = 0, bm_doubles = 0;
+  int n_ff = 0, n_mt = 0, n_tr = 0, n_tri = 0, n_m21 = 0;
+};
+// ... and what goes to the device once
+struct SweepPlan : SweepTables {
+  std::vector<int64_t> toff, ftoff;
+  std::vector<int> tri_pref, m_pref, tr_pref, mt_pref;
+  std::vector<FragFront> ffr;
+  std::vector<WgRec> fwd_wg, bwd_wg, pre_wg, wave_wg;
+  std::vector<int> ov_dst, ov_ptr, ov_src;
+  std::vector<int> bout, cmask;
+};
 
 }  // namespace eigd
 
 using namespace eigd;
 
 // ---------------------------------------------------------------------------
-struct eigd_factor {
+struct eigd_factor : SweepTables {
   eigd_ctx* ctx = nullptr;
   const Symbolic* sym = nullptr;  // borrowed; the Python wrapper keeps the symbolic object alive
   // device copies of the symbolic arrays
@@ -2255,78 +2323,42 @@ struct eigd_factor {
   int *d_lvl_fronts = nullptr, *d_pref_chunks = nullptr, *d_pref_tiles = nullptr, *d_cs_child = nullptr;
   // sweeps: per-level workgroup prefixes (forward: row tiles of [T; M21], backward: column tiles), gather lists
   WgRec *d_fwd_wg = nullptr, *d_bwd_wg = nullptr;
-  int *d_tri_pref = nullptr, *d_m_pref = nullptr, *d_bout = nullptr, *d_tickets = nullptr;
-  double* d_P = nullptr;
-  int64_t n_slabs = 0;
-  int n_tickets = 0;
+  int *d_tri_pref = nullptr, *d_m_pref = nullptr, *d_bout = nullptr;
   int *d_ov_dst = nullptr, *d_ov_ptr = nullptr, *d_ov_src = nullptr;
-  int nslot = 0, nplanes = 0;        // planes the parents read; planes allocated (+ scratch when there are surplus children)
   int64_t* d_toff = nullptr;
-  double *d_T = nullptr, *d_aux = nullptr;  // aux: {0.0, (int) -1}
-  double* d_red = nullptr;                  // 512 partial results of small reductions
-  std::vector<int> h_fwd_ptr, h_bwd_ptr;  // per level: first workgroup record
-  std::vector<int> h_thin_fwd, h_thin_bwd;  // per level: 4, 8 or 16 K-steps (of 4 own columns) of the wave-per-block kernels, 0: the tile kernels
-  std::vector<int> h_fwd_kd, h_bwd_kd;    // per level: LDS tile rows of the single-column-tile launches (multiple of 8)
-  std::vector<char> h_lvl_two;            // per level: every front has at most two children (two-plane kernels)
-  std::vector<char> h_lvl_leaf;           // per level: no front has children (kernels without carry loads)
-  std::vector<int> h_fwd_nsingle;         // per level: leading records of single-column-tile fronts (own kernel)
-  // levels whose multi-tile fronts get v1 pre-assembled (v1_assemble_kernel): one record per front and column tile
+  double* d_aux = nullptr;  // {0.0, (int) -1}
+  double* d_red = nullptr;  // 512 partial results of small reductions
   WgRec* d_pre_wg = nullptr;
-  std::vector<int> h_pre_ptr;             // per level: first record (none: the level's workgroups gather v1 themselves)
-  bool has_v1 = false;                    // one more plane per sweep width, behind all carry planes: receives v1
-  std::vector<int> h_bwd_nsingle;         // per level: leading backward records of single-column-tile fronts
-  std::vector<int> h_bwd_mxbs;            // per level: the longest border among the fronts with several column tiles
-  // narrow sweeps (k <= 8): one record per single-tile front and level, the transposed copy of [T; M21]
   WgRec* d_wave_wg = nullptr;
-  std::vector<int> h_wave_ptr;
   int64_t* d_ftoff = nullptr;
   int* d_tr_pref = nullptr;
-  double* d_Ft = nullptr;
   double* d_Fb = nullptr;  // [T; M21] in blocks of 16 rows, each block column-major (thin forward kernels: one contiguous piece per MFMA operand load)
-  double *d_Fm = nullptr, *d_Bm = nullptr;  // fragment-major copies (fronts with several column tiles)
+  double* d_Fm = nullptr;  // fragment-major copy (fronts with several column tiles)
   FragFront* d_ff = nullptr;
   int* d_mt_pref = nullptr;
-  int n_ff = 0, n_mt = 0;
-  int64_t fm_doubles = 0, bm_doubles = 0;
-  int64_t ft_doubles = 0;
-  int n_tr = 0;
-  std::vector<int> ov_lvl_ptr;       // per level: range of overflow rows (extra rows of V after the sumd front rows)
-  int64_t t_doubles = 0, v_rows = 0;
-  int n_tri = 0, n_m21 = 0;
-  int64_t *d_a_src = nullptr, *d_a_dst = nullptr;
   int* d_v_src = nullptr;
   int* d_cmask = nullptr;
-  double *d_data = nullptr, *d_F = nullptr, *d_Inv = nullptr, *d_V = nullptr, *d_Y = nullptr, *d_sgn = nullptr;
+  double *d_data = nullptr, *d_sgn = nullptr;
+  int* d_flag = nullptr;
+  // L side; an LU factor of an unsymmetric matrix (eigd_factor_create_lu) has a U side too: the sweeps read forward
+  // the L side, backward the U side.  Fb and Fm are forward copies: the L side's
+  FactorSide L, U;
+  SweepWorkspace ws;                // of the factor's own stream
+  std::vector<DeviceBuffer> bufs;   // every device array above
+  size_t bytes = 0;
   int n_negative = 0;
   int n_perturbed = 0;     // static pivots of the Bunch-Kaufman path (columns singular inside their panel block)
   double pivtol = 0.0;
   bool pivoted = false;  // the last numeric phase ran the Bunch-Kaufman panel kernel (dense diagonal blocks in T)
-  int* d_flag = nullptr;
-  size_t bytes = 0;
-  std::vector<int> ea_split;  // per (level, slot): grid.y of the extend-add launches
   int64_t data_len = 0;
   bool record_sweeps = false;  // solves of the factor and of its lanes record their launches (tests)
-  SweepRecord rec;             // ... those of the factor's own stream
-  // LU factor of an unsymmetric matrix (eigd_factor_create_lu): the U side has buffers of its own -- the transposed
-  // upper triangles FU, inv(U)^T per panel, T and the copies the backward sweep reads; the L side uses the ones above
   bool lu = false;
-  double *d_FU = nullptr, *d_InvU = nullptr, *d_TU = nullptr, *d_FtU = nullptr, *d_BmU = nullptr;
-  int64_t *d_u_src = nullptr, *d_u_dst = nullptr;  // scatter of the strictly upper entries into FU
-  int64_t nupper = 0;
   int n_interchanges = 0;  // row interchanges of the LU panels
 
   // the arrays the sweeps read: forward from the L side, backward from the U side (the same ones for L S L^T)
   SweepCopies copies() const {
-    SweepCopies c;
-    c.fF = d_F;
-    c.fT = d_T;
-    c.Fb = d_Fb;
-    c.Fm = d_Fm;
-    c.bF = lu ? d_FU : d_F;
-    c.bT = lu ? d_TU : d_T;
-    c.Ft = lu ? d_FtU : d_Ft;
-    c.Bm = lu ? d_BmU : d_Bm;
-    return c;
+    const FactorSide& b = lu ? U : L;
+    return SweepCopies{L.F, L.T, d_Fb, d_Fm, b.F, b.T, b.Ft, b.Bm};
   }
 
   FrontArrays fa() const {
@@ -2356,15 +2388,50 @@ struct eigd_factor {
   }
 };
 
+// A lane = a second sweep workspace bound to another context (stream) of the same device: sweeps of
+// different lanes run concurrently on the one factor (independent mode groups overlap each other's latency).
+struct eigd_lane {
+  eigd_factor* f = nullptr;
+  eigd_ctx* ctx = nullptr;
+  SweepWorkspace ws;
+  std::vector<DeviceBuffer> bufs;  // ws's (workspace_buffers)
+};
+
 namespace {
 
-template <typename T>
-int upload(eigd_factor* f, T** dptr, const std::vector<T>& h) {
-  size_t bytes = sizeof(T) * std::max<size_t>(h.size(), 1);
-  EIGD_HIP(hipMalloc(reinterpret_cast<void**>(dptr), bytes));
-  f->bytes += bytes;
-  if (!h.empty()) EIGD_HIP(hipMemcpy(*dptr, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+// allocates the buffers of t in order, uploads or zeroes them and adds their bytes; on failure what was allocated
+// stays for release()
+int allocate(std::vector<DeviceBuffer>& t, hipStream_t st, size_t& bytes) {
+  for (DeviceBuffer& b : t) {
+    const hipError_t e = hipMalloc(b.ptr, b.bytes());
+    if (e != hipSuccess) {
+      set_error("hipMalloc of %.2f GiB (%s) failed: %s", b.bytes() / 1073741824.0, b.name, hipGetErrorString(e));
+      return EIGD_E_HIP;
+    }
+    bytes += b.bytes();
+    if (b.host != nullptr && b.count > 0) EIGD_HIP(hipMemcpy(*b.ptr, b.host, b.elem * b.count, hipMemcpyHostToDevice));
+    b.host = nullptr;
+    if (b.zero) EIGD_HIP(hipMemsetAsync(*b.ptr, 0, b.bytes(), st));
+  }
   return EIGD_OK;
+}
+
+void release(const std::vector<DeviceBuffer>& t) {
+  for (const DeviceBuffer& b : t)
+    if (*b.ptr) {
+      (void)hipFree(*b.ptr);
+      *b.ptr = nullptr;
+    }
+}
+
+// the buffers of a sweep workspace of f: the factor's own are part of its table (in their place of the allocation
+// order), a lane keeps its own table
+std::vector<DeviceBuffer> workspace_buffers(SweepWorkspace& w, const eigd_factor& f) {
+  // (the carry planes start zeroed: entries no child writes must read as zero, in every sweep)
+  return {device_buffer("P", w.P, f.n_slabs * TW * KBMAX),
+          device_buffer("tickets", w.tickets, f.n_tickets, true),
+          device_buffer("V", w.V, static_cast<int64_t>(f.nplanes) * f.v_rows * kPlaneCols, true),
+          device_buffer("Y", w.Y, f.sym->sumd * KBMAX)};
 }
 
 // sqrt(eps) * max |a_ij| of the values on the device: the threshold of the static pivots
@@ -2381,38 +2448,40 @@ int static_pivot_tolerance(eigd_factor* f, hipStream_t st) {
   return EIGD_OK;
 }
 
-// numeric phase of an LU factor (see lu_inv_kernel): the same level and panel schedule as the symmetric one, every
-// step on both triangles
-int numeric_lu(eigd_factor* f, const double* data, bool on_device) {
+// Numeric phase: Cholesky, Bunch-Kaufman (pivot: the retry after a Cholesky pass that found the matrix indefinite) or,
+// for an LU factor, LU with row interchanges inside the panels (see lu_inv_kernel).  An LU factor runs every step on
+// both triangles, in the same level and panel schedule; only the panel step differs between the kinds.
+int numeric(eigd_factor* f, const double* data, bool on_device = false, bool pivot = false) {
   const Symbolic& s = *f->sym;
   hipStream_t st = f->ctx->stream;
-  f->pivoted = true;  // dense diagonal blocks of T on the L side
-  EIGD_HIP(hipMemcpyAsync(f->d_data, data, sizeof(double) * f->data_len,
-                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  EIGD_HIP(hipMemsetAsync(f->d_F, 0, sizeof(double) * s.front_doubles, st));
-  EIGD_HIP(hipMemsetAsync(f->d_FU, 0, sizeof(double) * s.front_doubles, st));
+  const bool lu = f->lu;
+  FactorSide* const sides[2] = {&f->L, &f->U};
+  const int nsides = lu ? 2 : 1;
+  f->pivoted = pivot || lu;  // (LU: dense diagonal blocks of T on the L side)
+  if (data != nullptr)  // (the pivoting pass re-reads the values the first pass brought in)
+    EIGD_HIP(hipMemcpyAsync(f->d_data, data, sizeof(double) * f->data_len,
+                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  for (int i = 0; i < nsides; ++i) EIGD_HIP(hipMemsetAsync(sides[i]->F, 0, sizeof(double) * s.front_doubles, st));
   EIGD_HIP(hipMemsetAsync(f->d_flag, 0, 4 * sizeof(int), st));
-  int rc = static_pivot_tolerance(f, st);
-  if (rc != EIGD_OK) return rc;
-  {
-    const int nb = static_cast<int>(std::min<int64_t>((s.nlower + 255) / 256, 65536));
-    hipLaunchKernelGGL(scatter_a_kernel, dim3(std::max(nb, 1)), dim3(256), 0, st, s.nlower, f->d_a_src, f->d_a_dst,
-                       f->d_data, f->d_F);
-    EIGD_LAUNCH_CHECK();
-    const int nbu = static_cast<int>(std::min<int64_t>((f->nupper + 255) / 256, 65536));
-    hipLaunchKernelGGL(scatter_a_kernel, dim3(std::max(nbu, 1)), dim3(256), 0, st, f->nupper, f->d_u_src, f->d_u_dst,
-                       f->d_data, f->d_FU);
+  if (lu) {
+    const int rc = static_pivot_tolerance(f, st);
+    if (rc != EIGD_OK) return rc;
+  }
+  for (int i = 0; i < nsides; ++i) {
+    const FactorSide& sd = *sides[i];
+    const int nb = static_cast<int>(std::min<int64_t>((sd.nmap + 255) / 256, 65536));
+    hipLaunchKernelGGL(scatter_a_kernel, dim3(std::max(nb, 1)), dim3(256), 0, st, sd.nmap, sd.src, sd.dst, f->d_data, sd.F);
     EIGD_LAUNCH_CHECK();
   }
   const FrontArrays fa = f->fa();
   for (int l = 0; l < s.nlevels; ++l) {
-    for (int slot = 0; slot < s.maxslots; ++slot) {  // contribution blocks: both triangles
+    for (int slot = 0; slot < s.maxslots; ++slot) {
       const size_t rec = static_cast<size_t>(l) * s.maxslots + slot;
       const int cnt = s.cs_ptr[rec + 1] - s.cs_ptr[rec];
       if (cnt == 0) continue;
-      for (double* G : {f->d_F, f->d_FU}) {
+      for (int i = 0; i < nsides; ++i) {
         hipLaunchKernelGGL(extend_add_kernel, dim3(cnt, f->ea_split[rec]), dim3(kThreads), 0, st, fa,
-                           f->d_cs_child + s.cs_ptr[rec], G);
+                           f->d_cs_child + s.cs_ptr[rec], sides[i]->F);
         EIGD_LAUNCH_CHECK();
       }
     }
@@ -2423,28 +2492,38 @@ int numeric_lu(eigd_factor* f, const double* data, bool on_device) {
       const int64_t po = s.ls_pref_ptr[rec];
       const int nchunks = s.pref_chunks[po + na];
       const int ntiles = s.pref_tiles[po + na];
-      hipLaunchKernelGGL(lu_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->d_F, f->d_FU, f->d_Inv,
-                         f->d_InvU, f->d_flag);
+      if (lu)
+        hipLaunchKernelGGL(lu_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->L.F, f->U.F, f->L.Inv,
+                           f->U.Inv, f->d_flag);
+      else if (pivot)
+        hipLaunchKernelGGL(ldlt_bk_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->L.F, f->L.Inv,
+                           f->d_flag);
+      else
+        hipLaunchKernelGGL(potrf_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->L.F, f->L.Inv,
+                           f->d_flag);
       EIGD_LAUNCH_CHECK();
       if (nchunks > 0) {
         hipLaunchKernelGGL(trsm_kernel, dim3(nchunks), dim3(kThreads), 0, st, fa, fronts, na, step,
-                           f->d_pref_chunks + po, f->d_F, f->d_InvU);  // L21 = A21 inv(U)
+                           f->d_pref_chunks + po, f->L.F, lu ? f->U.Inv : f->L.Inv);  // (LU: L21 = A21 inv(U))
         EIGD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(trsm_kernel, dim3(nchunks), dim3(kThreads), 0, st, fa, fronts, na, step,
-                           f->d_pref_chunks + po, f->d_FU, f->d_Inv);  // U12^T = A12^T inv(M_L)^T
-        EIGD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(lu_update_kernel, dim3(ntiles), dim3(kThreads), 0, st, fa, fronts, na, step,
-                           f->d_pref_chunks + po, f->d_pref_tiles + po, f->d_F, f->d_FU);
+        if (lu) {
+          hipLaunchKernelGGL(trsm_kernel, dim3(nchunks), dim3(kThreads), 0, st, fa, fronts, na, step,
+                             f->d_pref_chunks + po, f->U.F, f->L.Inv);  // U12^T = A12^T inv(M_L)^T
+          EIGD_LAUNCH_CHECK();
+          hipLaunchKernelGGL(lu_update_kernel, dim3(ntiles), dim3(kThreads), 0, st, fa, fronts, na, step,
+                             f->d_pref_chunks + po, f->d_pref_tiles + po, f->L.F, f->U.F);
+        } else
+          hipLaunchKernelGGL(syrk_kernel, dim3(ntiles), dim3(kThreads), 0, st, fa, fronts, na, step,
+                             f->d_pref_chunks + po, f->d_pref_tiles + po, f->L.F);
         EIGD_LAUNCH_CHECK();
       }
     }
   }
-  // T and M21 of both sides; then the copies.  The copy kernels write the forward and the backward copies together:
-  // the U side goes first, and what it leaves in the forward copies (Fb, Fm) the L side overwrites entry for entry;
-  // the L side's backward copies land in Ft / Bm, which an LU factor's sweeps do not read
-  struct Side { double *F, *Inv, *T, *Ft, *Bm; };
-  const Side sides[2] = {{f->d_FU, f->d_InvU, f->d_TU, f->d_FtU, f->d_BmU}, {f->d_F, f->d_Inv, f->d_T, f->d_Ft, f->d_Bm}};
-  for (const Side& sd : sides) {
+  // T and M21 of every side; then the copies.  The copy kernels write the forward and the backward copies together:
+  // an LU factor's U side goes first, and what it leaves in the forward copies (Fb, Fm) the L side overwrites entry
+  // for entry; the L side's backward copies land in Ft / Bm, which an LU factor's sweeps do not read
+  for (int i = nsides - 1; i >= 0; --i) {
+    const FactorSide& sd = *sides[i];
     if (f->n_tri > 0) {
       hipLaunchKernelGGL(trinv_kernel, dim3(f->n_tri), dim3(kThreads), 0, st, fa, f->d_tri_pref, s.nfronts, sd.F, sd.Inv,
                          sd.T);
@@ -2465,107 +2544,29 @@ int numeric_lu(eigd_factor* f, const double* data, bool on_device) {
       EIGD_LAUNCH_CHECK();
     }
   }
-  int flag[4] = {0, 0, 0, 0};
+  int flag[4] = {0, 0, 0, 0};  // first failed front + 1, negative pivots, static pivots, row interchanges
   EIGD_HIP(hipMemcpyAsync(flag, f->d_flag, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-  EIGD_HIP(hipStreamSynchronize(st));
-  f->n_negative = 0;
-  f->n_perturbed = flag[2];
-  f->n_interchanges = flag[3];
-  if (flag[0] != 0) {
-    set_error("non-finite entries in front %d: the matrix is singular to working precision or holds inf / NaN",
-              flag[0] - 1);
-    return EIGD_E_NOTSPD;
-  }
-  return EIGD_OK;
-}
-
-int numeric(eigd_factor* f, const double* data, bool on_device = false, bool pivot = false) {
-  if (f->lu) return numeric_lu(f, data, on_device);
-  const Symbolic& s = *f->sym;
-  hipStream_t st = f->ctx->stream;
-  f->pivoted = pivot;
-  if (data != nullptr)  // (the pivoting pass re-reads the values the first pass brought in)
-    EIGD_HIP(hipMemcpyAsync(f->d_data, data, sizeof(double) * f->data_len,
-                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  EIGD_HIP(hipMemsetAsync(f->d_F, 0, sizeof(double) * s.front_doubles, st));
-  EIGD_HIP(hipMemsetAsync(f->d_flag, 0, 3 * sizeof(int), st));
-  {
-    const int nb = static_cast<int>(std::min<int64_t>((s.nlower + 255) / 256, 65536));
-    hipLaunchKernelGGL(scatter_a_kernel, dim3(std::max(nb, 1)), dim3(256), 0, st, s.nlower, f->d_a_src, f->d_a_dst,
-                       f->d_data, f->d_F);
-    EIGD_LAUNCH_CHECK();
-  }
-  const FrontArrays fa = f->fa();
-  for (int l = 0; l < s.nlevels; ++l) {
-    for (int slot = 0; slot < s.maxslots; ++slot) {
-      const size_t rec = static_cast<size_t>(l) * s.maxslots + slot;
-      const int cnt = s.cs_ptr[rec + 1] - s.cs_ptr[rec];
-      if (cnt == 0) continue;
-      hipLaunchKernelGGL(extend_add_kernel, dim3(cnt, f->ea_split[rec]), dim3(kThreads), 0, st, fa,
-                         f->d_cs_child + s.cs_ptr[rec], f->d_F);
-      EIGD_LAUNCH_CHECK();
-    }
-    const int* fronts = f->d_lvl_fronts + s.lvl_ptr[l];
-    for (int step = 0; step < s.lvl_nsteps[l]; ++step) {
-      const int rec = s.ls_ptr[l] + step;
-      const int na = s.ls_nactive[rec];
-      const int64_t po = s.ls_pref_ptr[rec];
-      const int nchunks = s.pref_chunks[po + na];
-      const int ntiles = s.pref_tiles[po + na];
-      if (pivot)
-        hipLaunchKernelGGL(ldlt_bk_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->d_F, f->d_Inv,
-                           f->d_flag);
-      else
-        hipLaunchKernelGGL(potrf_inv_kernel, dim3(na), dim3(kThreads), 0, st, fa, fronts, step, f->d_F, f->d_Inv,
-                           f->d_flag);
-      EIGD_LAUNCH_CHECK();
-      if (nchunks > 0) {
-        hipLaunchKernelGGL(trsm_kernel, dim3(nchunks), dim3(kThreads), 0, st, fa, fronts, na, step,
-                           f->d_pref_chunks + po, f->d_F, f->d_Inv);
-        EIGD_LAUNCH_CHECK();
-        hipLaunchKernelGGL(syrk_kernel, dim3(ntiles), dim3(kThreads), 0, st, fa, fronts, na, step,
-                           f->d_pref_chunks + po, f->d_pref_tiles + po, f->d_F);
-        EIGD_LAUNCH_CHECK();
-      }
-    }
-  }
-  if (f->n_tri > 0) {
-    hipLaunchKernelGGL(trinv_kernel, dim3(f->n_tri), dim3(kThreads), 0, st, fa, f->d_tri_pref, s.nfronts, f->d_F,
-                       f->d_Inv, f->d_T);
-    EIGD_LAUNCH_CHECK();
-  }
-  if (f->n_m21 > 0) {
-    hipLaunchKernelGGL(m21_kernel, dim3(f->n_m21), dim3(kThreads), 0, st, fa, f->d_m_pref, s.nfronts, f->d_F, f->d_T);
-    EIGD_LAUNCH_CHECK();
-  }
-  if (f->n_tr > 0) {
-    hipLaunchKernelGGL(transpose_front_kernel, dim3(f->n_tr), dim3(kThreads), 0, st, fa, f->d_tr_pref, s.nfronts, f->d_ftoff,
-                       f->d_F, f->d_T, f->d_Ft, f->d_Fb);
-    EIGD_LAUNCH_CHECK();
-  }
-  if (f->n_mt > 0) {
-    hipLaunchKernelGGL(pack_frag_kernel, dim3(f->n_mt), dim3(kThreads), 0, st, fa, f->d_ff, f->d_mt_pref, f->n_ff, f->d_F,
-                       f->d_T, f->d_Fm, f->d_Bm);
-    EIGD_LAUNCH_CHECK();
-  }
-  int flag[3] = {0, 0, 0};
-  EIGD_HIP(hipMemcpyAsync(flag, f->d_flag, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
   EIGD_HIP(hipStreamSynchronize(st));
   f->n_negative = flag[1];
   f->n_perturbed = flag[2];
+  f->n_interchanges = flag[3];
   // Not positive definite (negative or unusable pivots on the Cholesky path): the shift lies inside the spectrum.
   // Factor again with Bunch-Kaufman pivoting inside the panels -- the positive definite shifts of the reference's
   // examples never come here and keep the plain (bitwise unchanged) Cholesky path.
-  if (!pivot && (flag[0] != 0 || flag[1] != 0)) {
+  if (!lu && !pivot && (flag[0] != 0 || flag[1] != 0)) {
     // the threshold of the static pivots: sqrt(eps) * max |a_ij| (the values are on the device: reduced there)
     const int rc = static_pivot_tolerance(f, st);
     if (rc != EIGD_OK) return rc;
     return numeric(f, nullptr, true, true);
   }
   if (flag[0] != 0) {
-    set_error("zero or non-finite pivot in front %d: the (shifted) matrix is singular to working precision -- move the "
-              "shift away from an eigenvalue",
-              flag[0] - 1);
+    if (lu)
+      set_error("non-finite entries in front %d: the matrix is singular to working precision or holds inf / NaN",
+                flag[0] - 1);
+    else
+      set_error("zero or non-finite pivot in front %d: the (shifted) matrix is singular to working precision -- move "
+                "the shift away from an eigenvalue",
+                flag[0] - 1);
     return EIGD_E_NOTSPD;
   }
   return EIGD_OK;
@@ -2577,6 +2578,390 @@ int pre_assembly_min_workgroups() {
   const char* e = std::getenv("EIGD_PRE_MIN_WG");
   const int v = e ? std::atoi(e) : 0;
   return v > 0 ? v : 512;
+}
+
+// Host planning of a factor: the copy layout, the workgroup records and launch tables of the sweeps, the carry planes
+// and the extend-add launch shapes.  No device work.
+SweepPlan plan_sweeps(const Symbolic& s, int pre_min_wg) {
+  SweepPlan p;
+  const int nf = s.nfronts;
+  p.toff.assign(static_cast<size_t>(nf) + 1, 0);
+  p.ftoff.assign(static_cast<size_t>(nf) + 1, 0);
+  p.tri_pref.assign(static_cast<size_t>(nf) + 1, 0);
+  p.m_pref.assign(static_cast<size_t>(nf) + 1, 0);
+  p.tr_pref.assign(static_cast<size_t>(nf) + 1, 0);
+  // The copies the sweeps read (Ft, Fb, Fm, Bm) are laid out LEVEL BY LEVEL, in the order the level's workgroups take
+  // their fronts: a launch streams one contiguous region (in front order, a postorder, the 8192 six-KB blocks of the
+  // level above the leaves lay 128 KB apart in a 1 GB array).  Measured neutral on the mean sweep time; the +-2 % by
+  // which a sweep's time moves with where a factor's arrays landed are there in either layout (docs/LOG.md, round 5).
+  {
+    int64_t acc = 0;
+    for (int l = 0; l < s.nlevels; ++l)
+      for (int q = s.lvl_ptr[l]; q < s.lvl_ptr[l + 1]; ++q) {
+        const int fr = s.lvl_fronts[q];
+        p.ftoff[fr] = acc;
+        acc += static_cast<int64_t>(s.f_ns[fr] + s.f_bs[fr]) * s.f_ns[fr];
+      }
+    p.ftoff[nf] = acc;  // (the total; entries 0 .. nf - 1 are per front, not a prefix array any more)
+  }
+  for (int q = 0; q < nf; ++q) {
+    const int64_t ns = s.f_ns[q];
+    const int64_t dq = ns + s.f_bs[q];
+    p.tr_pref[q + 1] = p.tr_pref[q] + static_cast<int>(((dq + TW - 1) / TW) * ((ns + TW - 1) / TW));
+    p.toff[q + 1] = p.toff[q] + ns * ns;
+    p.tri_pref[q + 1] = p.tri_pref[q] + static_cast<int>((ns + s.W - 1) / s.W);
+    p.m_pref[q + 1] = p.m_pref[q] + (s.f_bs[q] + TW - 1) / TW;
+  }
+  // fragment-major copies for the fronts with several column tiles (see pack_frag_kernel)
+  p.mt_pref.assign(1, 0);
+  std::vector<int> ff_of(static_cast<size_t>(nf), -1);
+  for (int lq = 0; lq < nf; ++lq) {  // (level by level as well)
+    const int q = s.lvl_fronts[lq];
+    const int ns = s.f_ns[q], bs = s.f_bs[q];
+    const int nst = (ns + TW - 1) / TW, nbt = (bs + TW - 1) / TW;
+    if (nst < 2) continue;
+    FragFront r;
+    r.f = q;
+    r.nst = nst;
+    r.nbt = nbt;
+    r.nko = (ns - TW * (nst - 1) + 3) / 4;
+    r.nkb = (nbt > 0) ? (bs - TW * (nbt - 1) + 3) / 4 : 0;
+    r.pad = 0;
+    r.fm = p.fm_doubles;
+    r.bm = p.bm_doubles;
+    p.fm_doubles += 256 * frag_fwd_steps(nst, r.nko, nst + nbt);
+    p.bm_doubles += 256 * frag_bwd_steps(nst, nbt, r.nko, r.nkb, nst);
+    ff_of[q] = static_cast<int>(p.ffr.size());
+    p.ffr.push_back(r);
+    p.mt_pref.push_back(p.mt_pref.back() + (nst + nbt) * nst);
+  }
+  // carry planes: child number q of a front (ascending front order) writes plane q; children beyond kMaxS write
+  // the scratch plane and are summed into the extra plane (overflow_sum_kernel) before their parent's level runs
+  std::vector<int> child_no(static_cast<size_t>(nf), 0), nchild(static_cast<size_t>(nf), 0);
+  int maxchild = 0;
+  for (int c = 0; c < nf; ++c) {
+    const int par = s.f_parent[c];
+    if (par < 0 || s.f_bs[c] == 0) continue;
+    child_no[c] = nchild[par]++;
+    maxchild = std::max(maxchild, nchild[par]);
+  }
+  const bool surplus = maxchild > kMaxS;
+  const int ndirect = std::min(maxchild, kMaxS);
+  const int nslot = ndirect + (surplus ? 1 : 0);
+  p.nslot = nslot;
+  p.nplanes = std::max(1, nslot + (surplus ? 1 : 0));   // (+ 1 below: the plane of pre-assembled right-hand sides)
+  struct Extra { int level; int dst; std::vector<int> src; };
+  std::vector<Extra> extras;
+  if (surplus) {
+    std::vector<int64_t> extra_of(static_cast<size_t>(s.sumd), -1);
+    for (int c = 0; c < nf; ++c) {
+      const int par = s.f_parent[c];
+      if (par < 0 || child_no[c] < kMaxS) continue;
+      const int64_t b0 = s.f_bptr[c];
+      for (int i = 0; i < s.f_bs[c]; ++i) {
+        const int64_t dst = s.f_voff[par] + s.rel[b0 + i];
+        if (extra_of[dst] < 0) {
+          extra_of[dst] = static_cast<int64_t>(extras.size());
+          extras.push_back(Extra{s.f_level[par], static_cast<int>(dst), {}});
+        }
+        extras[extra_of[dst]].src.push_back(static_cast<int>(s.f_voff[c] + s.f_ns[c] + i));
+      }
+    }
+    std::stable_sort(extras.begin(), extras.end(), [](const Extra& a, const Extra& b) { return a.level < b.level; });
+  }
+  p.ov_lvl_ptr.assign(static_cast<size_t>(s.nlevels) + 1, 0);
+  {
+    // per level the ov_ptr entries are [count + 1] long so that a level's slice starts at its own offset
+    std::vector<int> lvl_cnt(static_cast<size_t>(s.nlevels), 0);
+    for (const Extra& e : extras) lvl_cnt[e.level] += 1;
+    // layout: ov_dst[x], ov_ptr[x] / ov_ptr[x + 1] with one shared trailing entry (offsets are absolute)
+    for (const Extra& e : extras) {
+      p.ov_dst.push_back(e.dst);
+      p.ov_ptr.push_back(static_cast<int>(p.ov_src.size()));
+      for (int q : e.src) p.ov_src.push_back(q);
+    }
+    p.ov_ptr.push_back(static_cast<int>(p.ov_src.size()));
+    for (int l = 0; l < s.nlevels; ++l) p.ov_lvl_ptr[l + 1] = p.ov_lvl_ptr[l] + lvl_cnt[l];
+  }
+  p.v_rows = s.sumd;
+
+  // workgroup records per level (see WgRec).  Levels with few fronts cut their long chains into groups.
+  std::vector<char> has_kids(static_cast<size_t>(nf), 0);
+  for (int c = 0; c < nf; ++c)
+    if (s.f_parent[c] >= 0 && s.f_bs[c] > 0) has_kids[s.f_parent[c]] = 1;
+  p.h_fwd_ptr.assign(static_cast<size_t>(s.nlevels) + 1, 0);
+  p.h_bwd_ptr.assign(static_cast<size_t>(s.nlevels) + 1, 0);
+  int64_t fwd_slabs = 0, bwd_slabs = 0;
+  int n_tickets = 0;
+  // chains longer than split_min tiles are cut into groups of about split_len tiles (at most split_maxg groups) on
+  // levels of at most split_nfl fronts (swept over eight settings on the benchmark: these stay the best)
+  constexpr int split_min = 3, split_len = 3, split_maxg = 12, split_nfl = 128;
+  auto front_numbers = [&](WgRec& w, int fr) {
+    w.f = fr;
+    w.ns = s.f_ns[fr];
+    w.bs = s.f_bs[fr];
+    w.c0 = s.f_c0[fr];
+    w.voff = s.f_voff[fr];
+    w.foff = s.f_foff[fr];
+    w.toff = p.toff[fr];
+    w.ldt = s.f_ns[fr];
+    w.bptr = s.f_bptr[fr];
+    w.ftoff = p.ftoff[fr];
+    w.moff = 0;
+    const int par = s.f_parent[fr];
+    w.pvoff = (par >= 0) ? s.f_voff[par] : -1;
+    w.scratch = (child_no[fr] >= kMaxS) ? 1 : 0;
+    w.slot = w.scratch ? nslot : child_no[fr];
+  };
+  auto push_chain = [&](std::vector<WgRec>& out, int64_t& slabs, int fr, int tile, int L, bool split, int flags,
+                        bool backward) {
+    const int G = (split && L > split_min) ? std::min(split_maxg, (L + split_len - 1) / split_len) : 1;
+    int64_t moff = 0;  // the chain's first tile in the fragment-major copy
+    if (ff_of[fr] >= 0) {
+      const FragFront& r = p.ffr[ff_of[fr]];
+      moff = backward ? r.bm + 256 * frag_bwd_steps(r.nst, r.nbt, r.nko, r.nkb, tile)
+                      : r.fm + 256 * frag_fwd_steps(r.nst, r.nko, tile);
+    }
+    for (int g = 0; g < G; ++g) {
+      WgRec w;
+      front_numbers(w, fr);
+      w.moff = moff;
+      w.tile = tile;
+      w.s0 = static_cast<int>(static_cast<int64_t>(L) * g / G);
+      w.s1 = static_cast<int>(static_cast<int64_t>(L) * (g + 1) / G);
+      w.slab = static_cast<int>(slabs);
+      w.cnt = n_tickets;
+      w.G = G;
+      w.flags = flags | (g << 8);
+      out.push_back(w);
+    }
+    if (G > 1) {
+      slabs += G;
+      ++n_tickets;
+    }
+  };
+  p.h_fwd_nsingle.assign(static_cast<size_t>(s.nlevels), 0);
+  p.h_bwd_nsingle.assign(static_cast<size_t>(s.nlevels), 0);
+  p.h_pre_ptr.assign(static_cast<size_t>(s.nlevels) + 1, 0);
+  p.h_wave_ptr.assign(static_cast<size_t>(s.nlevels) + 1, 0);
+  std::vector<WgRec>& fwd_wg = p.fwd_wg;
+  std::vector<WgRec>& bwd_wg = p.bwd_wg;
+  for (int l = 0; l < s.nlevels; ++l) {
+    std::vector<WgRec> multi, bmulti, pre_lvl;
+    const int nfl = s.lvl_ptr[l + 1] - s.lvl_ptr[l];
+    const bool sparse_level = nfl < 256;  // few fronts: parallelism has to come from inside the fronts
+    const bool split_level = nfl <= split_nfl;   // the join of split chains costs an agent-scope acquire: only where chains are long
+    for (int q = s.lvl_ptr[l]; q < s.lvl_ptr[l + 1]; ++q) {
+      const int fr = s.lvl_fronts[q];
+      const int nst = (s.f_ns[fr] + TW - 1) / TW, nbt = (s.f_bs[fr] + TW - 1) / TW;
+      const int kids = has_kids[fr] ? 2 : 0;
+      if (nst == 1) {  // single column tile: the right-hand side block is loaded once per workgroup
+        {
+          WgRec w;  // narrow sweeps: one record per front, waves take the row tiles
+          front_numbers(w, fr);
+          w.tile = 0;
+          w.s0 = 0;
+          w.s1 = nst + nbt;
+          w.slab = w.cnt = 0;
+          w.G = 1;
+          w.flags = 1 | kids;
+          p.wave_wg.push_back(w);
+        }
+        const int per = sparse_level ? 1 : nst + nbt;
+        for (int t = 0; t < nst + nbt; t += per) {
+          WgRec w;
+          front_numbers(w, fr);
+          w.tile = 0;
+          w.s0 = t;
+          w.s1 = std::min(nst + nbt, t + per);
+          w.slab = w.cnt = 0;
+          w.G = 1;
+          w.flags = 1 | kids;
+          fwd_wg.push_back(w);
+        }
+      } else {
+        for (int t = nst + nbt - 1; t >= 0; --t)  // border tiles (nst products) first, then the own tiles, longest first
+          push_chain(multi, fwd_slabs, fr, t, t < nst ? t + 1 : nst, split_level, kids, false);
+        for (int t = 0; t < nst; ++t) {
+          WgRec w;
+          front_numbers(w, fr);
+          w.tile = t;
+          w.s0 = w.s1 = 0;
+          w.slab = w.cnt = 0;
+          w.G = 1;
+          w.flags = kids;
+          pre_lvl.push_back(w);
+        }
+      }
+      const int nbt_b = (s.f_parent[fr] >= 0) ? nbt : 0;
+      for (int t = 0; t < nst; ++t)
+        // (a single-column-tile front is never split: the wave kernels run it in one piece, and a column's solution
+        // must not depend on the width of the sweep it is part of)
+        push_chain(nst == 1 ? bwd_wg : bmulti, bwd_slabs, fr, t, nst - t + nbt_b, split_level && nst > 1, 0, true);
+    }
+    p.h_fwd_nsingle[l] = static_cast<int>(fwd_wg.size()) - p.h_fwd_ptr[l];
+    p.h_bwd_nsingle[l] = static_cast<int>(bwd_wg.size()) - p.h_bwd_ptr[l];
+    bwd_wg.insert(bwd_wg.end(), bmulti.begin(), bmulti.end());
+    p.h_wave_ptr[l + 1] = static_cast<int>(p.wave_wg.size());
+    fwd_wg.insert(fwd_wg.end(), multi.begin(), multi.end());
+    p.h_fwd_ptr[l + 1] = static_cast<int>(fwd_wg.size());
+    // v1 written once per level where the row-tile workgroups that would each gather it are more than the chip holds at
+    // two waves per SIMD (512): the pre-assembled form runs three, and drops an index round from every workgroup.  The
+    // shell model's levels of 4000 to 14000: -30 % per launch; the 1 M-dof column's five levels of 552 to 1984: 1.43 ->
+    // 1.36 ms per 32-column sweep (four factors in one process, tools/pre_ab_probe.py).  Below that the extra launch
+    // costs more than the round it saves
+    if (static_cast<int>(multi.size()) >= pre_min_wg)
+      p.pre_wg.insert(p.pre_wg.end(), pre_lvl.begin(), pre_lvl.end());
+    p.h_pre_ptr[l + 1] = static_cast<int>(p.pre_wg.size());
+    p.h_bwd_ptr[l + 1] = static_cast<int>(bwd_wg.size());
+  }
+  p.n_slabs = std::max<int64_t>(1, std::max(fwd_slabs, bwd_slabs));
+  p.n_tickets = std::max(1, n_tickets);
+  p.has_v1 = !p.pre_wg.empty();
+  if (p.has_v1) p.nplanes += 1;
+  // rows of the caller's block behind every border entry (backward sweep gathers x there)
+  p.bout.resize(s.border.size());
+  for (size_t e = 0; e < s.border.size(); ++e) p.bout[e] = s.perm[s.border[e]];
+  p.h_lvl_leaf.assign(static_cast<size_t>(s.nlevels), 1);
+  for (int q = 0; q < nf; ++q)
+    if (nchild[q] > 0) p.h_lvl_leaf[s.f_level[q]] = 0;
+  p.h_lvl_two.assign(static_cast<size_t>(s.nlevels), 1);
+  for (int q = 0; q < nf; ++q)
+    if (nchild[q] > 2) p.h_lvl_two[s.f_level[q]] = 0;
+  p.h_bwd_mxbs.assign(static_cast<size_t>(s.nlevels), 0);
+  for (int q = 0; q < nf; ++q)
+    if (s.f_ns[q] > TW && s.f_parent[q] >= 0)
+      p.h_bwd_mxbs[s.f_level[q]] = std::max<int>(p.h_bwd_mxbs[s.f_level[q]], s.f_bs[q]);
+  p.h_fwd_kd.assign(static_cast<size_t>(s.nlevels), 8);
+  p.h_bwd_kd.assign(static_cast<size_t>(s.nlevels), 8);
+  {
+    // levels for the wave-per-block kernels: every single-column-tile front has at most thin_fwd / thin_bwd own
+    // columns and (backward) a border of <= 320
+    constexpr int thin_fwd = TW, thin_bwd = TW;
+    std::vector<int> mxns(static_cast<size_t>(s.nlevels), 0), mxbs(static_cast<size_t>(s.nlevels), 0);
+    for (int q = 0; q < nf; ++q) {
+      if (s.f_ns[q] > TW) continue;
+      mxns[s.f_level[q]] = std::max<int>(mxns[s.f_level[q]], s.f_ns[q]);
+      mxbs[s.f_level[q]] = std::max<int>(mxbs[s.f_level[q]], s.f_bs[q]);
+    }
+    p.h_thin_fwd.assign(static_cast<size_t>(s.nlevels), 0);
+    p.h_thin_bwd.assign(static_cast<size_t>(s.nlevels), 0);
+    for (int l = 0; l < s.nlevels; ++l) {
+      // (fronts with carry planes and 33 to 48 own columns: 12 K-steps -- the buffer-access kernels, several waves per front)
+      const int nks = (mxns[l] <= 16) ? 4 : (mxns[l] <= 32) ? 8 : (mxns[l] <= 48 && !p.h_lvl_leaf[l]) ? 12 : 16;
+      // leaf level: K-steps of the forward kernel cut to the widest front (12 / 14 instead of 16: fewer MFMAs on zeros)
+      const int nks_leaf = (mxns[l] > 32 && mxns[l] <= 48) ? 12 : (mxns[l] > 48 && mxns[l] <= 56) ? 14 : nks;
+      // (with carries to gather, the 16-step forward variant needs 244 VGPRs: those levels stay with the tile kernels)
+      // levels of binary fronts with up to 48 own columns go to the buffer-access thin
+      // kernels too, with two or four waves per front where the level has fewer than 2048 fronts (at C3 the two levels of
+      // 42-column fronts under the multi-tile ones: 61 + 44 us in the tile kernel)
+      const int kids_cap = p.h_lvl_two[l] ? 48 : 32;
+      if (mxns[l] > 0 && mxns[l] <= (p.h_lvl_leaf[l] ? thin_fwd : std::min(thin_fwd, kids_cap)))
+        p.h_thin_fwd[l] = p.h_lvl_leaf[l] ? nks_leaf : nks;
+      // (backward: one wave per front -- with more than 32 own columns only where the level has fronts enough to
+      // fill the chip that way)
+      const int nfl = p.h_wave_ptr[l + 1] - p.h_wave_ptr[l];
+      const int nks_b = (mxns[l] <= 16) ? 4 : (mxns[l] <= 32) ? 8 : 16;  // (the backward kernels know 4, 8 and 16 K-steps)
+      if (mxns[l] > 0 && mxns[l] <= thin_bwd && mxbs[l] <= 320 && (nks_b < 16 || nfl >= 1024)) p.h_thin_bwd[l] = nks_b;
+    }
+  }
+  for (int q = 0; q < nf; ++q) {
+    if (s.f_ns[q] > TW) continue;
+    const int l = s.f_level[q];
+    const int bsq = (s.f_parent[q] >= 0) ? std::min<int>(TW, s.f_bs[q]) : 0;
+    p.h_fwd_kd[l] = std::max(p.h_fwd_kd[l], (s.f_ns[q] + 7) & ~7);
+    p.h_bwd_kd[l] = std::max(p.h_bwd_kd[l], (std::max<int>(s.f_ns[q], bsq) + 7) & ~7);
+  }
+  p.t_doubles = p.toff[nf];
+  p.ft_doubles = p.ftoff[nf];
+  p.n_ff = static_cast<int>(p.ffr.size());
+  p.n_mt = p.mt_pref.back();
+  p.n_tr = p.tr_pref[nf];
+  p.n_tri = p.tri_pref[nf];
+  p.n_m21 = p.m_pref[nf];
+  {
+    // which carry planes hold a contribution on which row: child number q of a front writes plane q at the parent's
+    // rows rel(border); the summed surplus children arrive in plane nslot - 1
+    p.cmask.assign(static_cast<size_t>(s.sumd), 0);
+    for (int c = 0; c < nf; ++c) {
+      const int par = s.f_parent[c];
+      if (par < 0 || s.f_bs[c] == 0) continue;
+      const int bit = (child_no[c] >= kMaxS) ? nslot - 1 : child_no[c];
+      const int64_t b0 = s.f_bptr[c];
+      for (int i = 0; i < s.f_bs[c]; ++i) p.cmask[static_cast<size_t>(s.f_voff[par] + s.rel[b0 + i])] |= 1 << bit;
+    }
+  }
+  // extend-add launch shapes
+  p.ea_split.assign(static_cast<size_t>(s.nlevels) * s.maxslots, 1);
+  for (size_t rec = 0; rec + 1 < s.cs_ptr.size(); ++rec) {
+    int64_t maxbs = 1;
+    for (int q = s.cs_ptr[rec]; q < s.cs_ptr[rec + 1]; ++q) maxbs = std::max<int64_t>(maxbs, s.f_bs[s.cs_child[q]]);
+    int64_t split = (maxbs * maxbs + kThreads * 32 - 1) / (kThreads * 32);
+    p.ea_split[rec] = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(split, 512)));
+  }
+  return p;
+}
+
+// Every device array of a factor, in allocation order (where the large ones land moves the sweep times by about +-2 %:
+// their order stays put).  The host sources are p's and f's symbolic's, read once by allocate()
+std::vector<DeviceBuffer> factor_buffers(eigd_factor* f, const SweepPlan& p) {
+  const Symbolic& s = *f->sym;
+  static const int32_t aux[4] = {0, 0, -1, 0};  // d_aux: {0.0, (int) -1}
+  std::vector<DeviceBuffer> t = {
+      upload_buffer("f_c0", f->d_c0, s.f_c0),
+      upload_buffer("f_ns", f->d_ns, s.f_ns),
+      upload_buffer("f_bs", f->d_bs, s.f_bs),
+      upload_buffer("f_parent", f->d_parent, s.f_parent),
+      upload_buffer("rel", f->d_rel, s.rel),
+      upload_buffer("f_foff", f->d_foff, s.f_foff),
+      upload_buffer("f_voff", f->d_voff, s.f_voff),
+      upload_buffer("f_ioff", f->d_ioff, s.f_ioff),
+      upload_buffer("f_bptr", f->d_bptr, s.f_bptr),
+      upload_buffer("lvl_fronts", f->d_lvl_fronts, s.lvl_fronts),
+      upload_buffer("pref_chunks", f->d_pref_chunks, s.pref_chunks),
+      upload_buffer("pref_tiles", f->d_pref_tiles, s.pref_tiles),
+      upload_buffer("fwd_wg", f->d_fwd_wg, p.fwd_wg),
+      upload_buffer("bwd_wg", f->d_bwd_wg, p.bwd_wg),
+      upload_buffer("wave_wg", f->d_wave_wg, p.wave_wg),
+      upload_buffer("pre_wg", f->d_pre_wg, p.pre_wg),
+      upload_buffer("ftoff", f->d_ftoff, p.ftoff),
+      upload_buffer("tr_pref", f->d_tr_pref, p.tr_pref),
+      upload_buffer("mt_pref", f->d_mt_pref, p.mt_pref)};
+  if (!p.ffr.empty()) t.push_back(upload_buffer("ffr", f->d_ff, p.ffr));
+  t.insert(t.end(), {upload_buffer("bout", f->d_bout, p.bout),
+                     upload_buffer("tri_pref", f->d_tri_pref, p.tri_pref),
+                     upload_buffer("m_pref", f->d_m_pref, p.m_pref),
+                     upload_buffer("toff", f->d_toff, p.toff),
+                     upload_buffer("ov_dst", f->d_ov_dst, p.ov_dst),
+                     upload_buffer("ov_ptr", f->d_ov_ptr, p.ov_ptr),
+                     upload_buffer("ov_src", f->d_ov_src, p.ov_src),
+                     upload_buffer("cs_child", f->d_cs_child, s.cs_child),
+                     upload_buffer("a_src", f->L.src, s.a_src),
+                     upload_buffer("a_dst", f->L.dst, s.a_dst),
+                     upload_buffer("v_src", f->d_v_src, s.v_src)});
+  if (f->lu) t.insert(t.end(), {upload_buffer("u_src", f->U.src, s.u_src), upload_buffer("u_dst", f->U.dst, s.u_dst)});
+  t.insert(t.end(), {upload_buffer("cmask", f->d_cmask, p.cmask),
+                     device_buffer("data", f->d_data, f->data_len),
+                     device_buffer("F", f->L.F, s.front_doubles),
+                     device_buffer("Inv", f->L.Inv, s.inv_doubles, true),
+                     device_buffer("T", f->L.T, p.t_doubles, true),  // (upper triangles stay zero)
+                     DeviceBuffer{"aux", reinterpret_cast<void**>(&f->d_aux), sizeof(double), 2, false, aux},
+                     device_buffer("red", f->d_red, 512),
+                     device_buffer("Ft", f->L.Ft, p.ft_doubles),
+                     device_buffer("Fb", f->d_Fb, p.ft_doubles),
+                     device_buffer("Fm", f->d_Fm, p.fm_doubles),
+                     device_buffer("Bm", f->L.Bm, p.bm_doubles)});
+  const std::vector<DeviceBuffer> ws = workspace_buffers(f->ws, *f);
+  t.insert(t.end(), ws.begin(), ws.end());
+  t.push_back(device_buffer("sgn", f->d_sgn, s.n));
+  if (f->lu)
+    t.insert(t.end(), {device_buffer("FU", f->U.F, s.front_doubles),
+                       device_buffer("InvU", f->U.Inv, s.inv_doubles, true),
+                       device_buffer("TU", f->U.T, p.t_doubles, true),
+                       device_buffer("FtU", f->U.Ft, p.ft_doubles),
+                       device_buffer("BmU", f->U.Bm, p.bm_doubles)});
+  t.push_back(device_buffer("flag", f->d_flag, 4));
+  return t;
 }
 
 // Launch policy of the sweeps (all measured on the 1 M-dof benchmark; the experiments behind each number are in
@@ -2594,8 +2979,10 @@ constexpr int kWaveMaxKpt = 2;   // widest sweep (units of 4 columns) whose sing
   } while (0)
 
 template <int KPT>
-int sweep(eigd_factor* f, const SweepCopies& cp, hipStream_t st, double* wV, double* wY, double* wP, int* wT,
-          const double* dIn, int ldin, double* dX, int ldx, int kb, double alpha, SweepRecord* rec) {
+int sweep(eigd_factor* f, const SweepCopies& cp, hipStream_t st, const SweepWorkspace& ws, const double* dIn, int ldin,
+          double* dX, int ldx, int kb, double alpha, SweepRecord* rec) {
+  double *wV = ws.V, *wY = ws.Y, *wP = ws.P;
+  int* wT = ws.tickets;
   const Symbolic& s = *f->sym;
   const FrontArrays fa = f->fa();
   // every sweep width (KB = 4, 8, 16, 32 columns) has its own set of carry planes: rows are KB wide and the
@@ -2933,18 +3320,7 @@ int eigd_symbolic_get_i64(eigd_symbolic* h, const char* name, int64_t* out, int6
 int eigd_factor_free(eigd_factor* f) {
   if (!f) return EIGD_OK;
   if (f->ctx && f->ctx->stream) (void)hipStreamSynchronize(f->ctx->stream);
-  void* ptrs[] = {f->d_c0,        f->d_ns,          f->d_bs,         f->d_parent,   f->d_rel,   f->d_foff,
-                  f->d_voff,      f->d_ioff,        f->d_bptr,       f->d_lvl_fronts, f->d_pref_chunks,
-                  f->d_pref_tiles, f->d_cs_child,   f->d_a_src,      f->d_a_dst,    f->d_v_src, f->d_data,   f->d_cmask,
-                  f->d_F,         f->d_Inv,         f->d_V,          f->d_Y,        f->d_flag,  f->d_fwd_wg,
-                  f->d_bwd_wg,    f->d_tri_pref,    f->d_m_pref,     f->d_ov_dst,   f->d_ov_ptr, f->d_ov_src,
-                  f->d_toff,      f->d_T,           f->d_sgn,        f->d_aux,      f->d_bout,  f->d_tickets,
-                  f->d_P,         f->d_wave_wg,     f->d_ftoff,      f->d_tr_pref,  f->d_Ft,  f->d_Fb,
-                  f->d_Fm,        f->d_Bm,          f->d_ff,         f->d_mt_pref,  f->d_red,   f->d_pre_wg,
-                  f->d_FU,        f->d_InvU,        f->d_TU,         f->d_FtU,      f->d_BmU,   f->d_u_src,
-                  f->d_u_dst};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  release(f->bufs);
   delete f;
   return EIGD_OK;
 }
@@ -2957,476 +3333,35 @@ static int create_factor(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, e
     return EIGD_E_INVALID;
   }
   const Symbolic& s = h->s;
+  EIGD_REQUIRE(s.sumd < (int64_t(1) << 31), "vector workspace has too many rows");
   EIGD_HIP(hipSetDevice(ctx->device));
-  // ---- host tables of the sweeps
-  const int nf = s.nfronts;
-  std::vector<int64_t> toff(static_cast<size_t>(nf) + 1, 0), ftoff(static_cast<size_t>(nf) + 1, 0);
-  std::vector<int> tri_pref(static_cast<size_t>(nf) + 1, 0), m_pref(static_cast<size_t>(nf) + 1, 0);
-  std::vector<int> tr_pref(static_cast<size_t>(nf) + 1, 0);
-  // The copies the sweeps read (Ft, Fb, Fm, Bm) are laid out LEVEL BY LEVEL, in the order the level's workgroups take
-  // their fronts: a launch streams one contiguous region (in front order, a postorder, the 8192 six-KB blocks of the
-  // level above the leaves lay 128 KB apart in a 1 GB array).  Measured neutral on the mean sweep time; the +-2 % by
-  // which a sweep's time moves with where a factor's arrays landed are there in either layout (docs/LOG.md, round 5).
-  {
-    int64_t acc = 0;
-    for (int l = 0; l < s.nlevels; ++l)
-      for (int q = s.lvl_ptr[l]; q < s.lvl_ptr[l + 1]; ++q) {
-        const int fr = s.lvl_fronts[q];
-        ftoff[fr] = acc;
-        acc += static_cast<int64_t>(s.f_ns[fr] + s.f_bs[fr]) * s.f_ns[fr];
-      }
-    ftoff[nf] = acc;  // (the total; entries 0 .. nf - 1 are per front, not a prefix array any more)
-  }
-  for (int q = 0; q < nf; ++q) {
-    const int64_t ns = s.f_ns[q];
-    const int64_t dq = ns + s.f_bs[q];
-    tr_pref[q + 1] = tr_pref[q] + static_cast<int>(((dq + TW - 1) / TW) * ((ns + TW - 1) / TW));
-    toff[q + 1] = toff[q] + ns * ns;
-    tri_pref[q + 1] = tri_pref[q] + static_cast<int>((ns + s.W - 1) / s.W);
-    m_pref[q + 1] = m_pref[q] + (s.f_bs[q] + TW - 1) / TW;
-  }
-  // fragment-major copies for the fronts with several column tiles (see pack_frag_kernel)
-  std::vector<FragFront> ffr;
-  std::vector<int> mt_pref(1, 0), ff_of(static_cast<size_t>(nf), -1);
-  int64_t fm_doubles = 0, bm_doubles = 0;
-  for (int lq = 0; lq < nf; ++lq) {  // (level by level as well)
-    const int q = s.lvl_fronts[lq];
-    const int ns = s.f_ns[q], bs = s.f_bs[q];
-    const int nst = (ns + TW - 1) / TW, nbt = (bs + TW - 1) / TW;
-    if (nst < 2) continue;
-    FragFront r;
-    r.f = q;
-    r.nst = nst;
-    r.nbt = nbt;
-    r.nko = (ns - TW * (nst - 1) + 3) / 4;
-    r.nkb = (nbt > 0) ? (bs - TW * (nbt - 1) + 3) / 4 : 0;
-    r.pad = 0;
-    r.fm = fm_doubles;
-    r.bm = bm_doubles;
-    fm_doubles += 256 * frag_fwd_steps(nst, r.nko, nst + nbt);
-    bm_doubles += 256 * frag_bwd_steps(nst, nbt, r.nko, r.nkb, nst);
-    ff_of[q] = static_cast<int>(ffr.size());
-    ffr.push_back(r);
-    mt_pref.push_back(mt_pref.back() + (nst + nbt) * nst);
-  }
-  // carry planes: child number q of a front (ascending front order) writes plane q; children beyond kMaxS write
-  // the scratch plane and are summed into the extra plane (overflow_sum_kernel) before their parent's level runs
-  std::vector<int> child_no(static_cast<size_t>(nf), 0), nchild(static_cast<size_t>(nf), 0);
-  int maxchild = 0;
-  for (int c = 0; c < nf; ++c) {
-    const int p = s.f_parent[c];
-    if (p < 0 || s.f_bs[c] == 0) continue;
-    child_no[c] = nchild[p]++;
-    maxchild = std::max(maxchild, nchild[p]);
-  }
-  const bool surplus = maxchild > kMaxS;
-  const int ndirect = std::min(maxchild, kMaxS);
-  const int nslot = ndirect + (surplus ? 1 : 0);
-  int nplanes = std::max(1, nslot + (surplus ? 1 : 0));   // (+ 1 below: the plane of pre-assembled right-hand sides)
-  struct Extra { int level; int dst; std::vector<int> src; };
-  std::vector<Extra> extras;
-  if (surplus) {
-    std::vector<int64_t> extra_of(static_cast<size_t>(s.sumd), -1);
-    for (int c = 0; c < nf; ++c) {
-      const int p = s.f_parent[c];
-      if (p < 0 || child_no[c] < kMaxS) continue;
-      const int64_t b0 = s.f_bptr[c];
-      for (int i = 0; i < s.f_bs[c]; ++i) {
-        const int64_t dst = s.f_voff[p] + s.rel[b0 + i];
-        if (extra_of[dst] < 0) {
-          extra_of[dst] = static_cast<int64_t>(extras.size());
-          extras.push_back(Extra{s.f_level[p], static_cast<int>(dst), {}});
-        }
-        extras[extra_of[dst]].src.push_back(static_cast<int>(s.f_voff[c] + s.f_ns[c] + i));
-      }
-    }
-    std::stable_sort(extras.begin(), extras.end(), [](const Extra& a, const Extra& b) { return a.level < b.level; });
-  }
-  std::vector<int> ov_dst, ov_ptr, ov_src, ov_lvl_ptr(static_cast<size_t>(s.nlevels) + 1, 0);
-  {
-    // per level the ov_ptr entries are [count + 1] long so that a level's slice starts at its own offset
-    std::vector<int> lvl_cnt(static_cast<size_t>(s.nlevels), 0);
-    for (const Extra& e : extras) lvl_cnt[e.level] += 1;
-    // layout: ov_dst[x], ov_ptr[x] / ov_ptr[x + 1] with one shared trailing entry (offsets are absolute)
-    for (const Extra& e : extras) {
-      ov_dst.push_back(e.dst);
-      ov_ptr.push_back(static_cast<int>(ov_src.size()));
-      for (int q : e.src) ov_src.push_back(q);
-    }
-    ov_ptr.push_back(static_cast<int>(ov_src.size()));
-    for (int l = 0; l < s.nlevels; ++l) ov_lvl_ptr[l + 1] = ov_lvl_ptr[l] + lvl_cnt[l];
-  }
-  const int64_t v_rows = s.sumd;
-  EIGD_REQUIRE(v_rows < (int64_t(1) << 31), "vector workspace has too many rows");
-
-  // workgroup records per level (see WgRec).  Levels with few fronts cut their long chains into groups.
-  std::vector<char> has_kids(static_cast<size_t>(nf), 0);
-  for (int c = 0; c < nf; ++c)
-    if (s.f_parent[c] >= 0 && s.f_bs[c] > 0) has_kids[s.f_parent[c]] = 1;
-  std::vector<WgRec> fwd_wg, bwd_wg;
-  std::vector<int> h_fwd_ptr(static_cast<size_t>(s.nlevels) + 1, 0), h_bwd_ptr(static_cast<size_t>(s.nlevels) + 1, 0);
-  int64_t fwd_slabs = 0, bwd_slabs = 0;
-  int n_tickets = 0;
-  // chains longer than split_min tiles are cut into groups of about split_len tiles (at most split_maxg groups) on
-  // levels of at most split_nfl fronts (swept over eight settings on the benchmark: these stay the best)
-  constexpr int split_min = 3, split_len = 3, split_maxg = 12, split_nfl = 128;
-  auto front_numbers = [&](WgRec& w, int fr) {
-    w.f = fr;
-    w.ns = s.f_ns[fr];
-    w.bs = s.f_bs[fr];
-    w.c0 = s.f_c0[fr];
-    w.voff = s.f_voff[fr];
-    w.foff = s.f_foff[fr];
-    w.toff = toff[fr];
-    w.ldt = s.f_ns[fr];
-    w.bptr = s.f_bptr[fr];
-    w.ftoff = ftoff[fr];
-    w.moff = 0;
-    const int par = s.f_parent[fr];
-    w.pvoff = (par >= 0) ? s.f_voff[par] : -1;
-    w.scratch = (child_no[fr] >= kMaxS) ? 1 : 0;
-    w.slot = w.scratch ? nslot : child_no[fr];
-  };
-  auto push_chain = [&](std::vector<WgRec>& out, int64_t& slabs, int fr, int tile, int L, bool split, int flags,
-                        bool backward) {
-    const int G = (split && L > split_min) ? std::min(split_maxg, (L + split_len - 1) / split_len) : 1;
-    int64_t moff = 0;  // the chain's first tile in the fragment-major copy
-    if (ff_of[fr] >= 0) {
-      const FragFront& r = ffr[ff_of[fr]];
-      moff = backward ? r.bm + 256 * frag_bwd_steps(r.nst, r.nbt, r.nko, r.nkb, tile)
-                      : r.fm + 256 * frag_fwd_steps(r.nst, r.nko, tile);
-    }
-    for (int g = 0; g < G; ++g) {
-      WgRec w;
-      front_numbers(w, fr);
-      w.moff = moff;
-      w.tile = tile;
-      w.s0 = static_cast<int>(static_cast<int64_t>(L) * g / G);
-      w.s1 = static_cast<int>(static_cast<int64_t>(L) * (g + 1) / G);
-      w.slab = static_cast<int>(slabs);
-      w.cnt = n_tickets;
-      w.G = G;
-      w.flags = flags | (g << 8);
-      out.push_back(w);
-    }
-    if (G > 1) {
-      slabs += G;
-      ++n_tickets;
-    }
-  };
-  std::vector<int> h_fwd_nsingle(static_cast<size_t>(s.nlevels), 0), h_bwd_nsingle(static_cast<size_t>(s.nlevels), 0);
-  std::vector<WgRec> pre_wg;
-  std::vector<int> h_pre_ptr(static_cast<size_t>(s.nlevels) + 1, 0);
-  const int pre_min_wg = pre_assembly_min_workgroups();
-  std::vector<WgRec> wave_wg;
-  std::vector<int> h_wave_ptr(static_cast<size_t>(s.nlevels) + 1, 0);
-  for (int l = 0; l < s.nlevels; ++l) {
-    std::vector<WgRec> multi, bmulti, pre_lvl;
-    const int nfl = s.lvl_ptr[l + 1] - s.lvl_ptr[l];
-    const bool sparse_level = nfl < 256;  // few fronts: parallelism has to come from inside the fronts
-    const bool split_level = nfl <= split_nfl;   // the join of split chains costs an agent-scope acquire: only where chains are long
-    for (int q = s.lvl_ptr[l]; q < s.lvl_ptr[l + 1]; ++q) {
-      const int fr = s.lvl_fronts[q];
-      const int nst = (s.f_ns[fr] + TW - 1) / TW, nbt = (s.f_bs[fr] + TW - 1) / TW;
-      const int kids = has_kids[fr] ? 2 : 0;
-      if (nst == 1) {  // single column tile: the right-hand side block is loaded once per workgroup
-        {
-          WgRec w;  // narrow sweeps: one record per front, waves take the row tiles
-          front_numbers(w, fr);
-          w.tile = 0;
-          w.s0 = 0;
-          w.s1 = nst + nbt;
-          w.slab = w.cnt = 0;
-          w.G = 1;
-          w.flags = 1 | kids;
-          wave_wg.push_back(w);
-        }
-        const int per = sparse_level ? 1 : nst + nbt;
-        for (int t = 0; t < nst + nbt; t += per) {
-          WgRec w;
-          front_numbers(w, fr);
-          w.tile = 0;
-          w.s0 = t;
-          w.s1 = std::min(nst + nbt, t + per);
-          w.slab = w.cnt = 0;
-          w.G = 1;
-          w.flags = 1 | kids;
-          fwd_wg.push_back(w);
-        }
-      } else {
-        for (int t = nst + nbt - 1; t >= 0; --t)  // border tiles (nst products) first, then the own tiles, longest first
-          push_chain(multi, fwd_slabs, fr, t, t < nst ? t + 1 : nst, split_level, kids, false);
-        for (int t = 0; t < nst; ++t) {
-          WgRec w;
-          front_numbers(w, fr);
-          w.tile = t;
-          w.s0 = w.s1 = 0;
-          w.slab = w.cnt = 0;
-          w.G = 1;
-          w.flags = kids;
-          pre_lvl.push_back(w);
-        }
-      }
-      const int nbt_b = (s.f_parent[fr] >= 0) ? nbt : 0;
-      for (int t = 0; t < nst; ++t)
-        // (a single-column-tile front is never split: the wave kernels run it in one piece, and a column's solution
-        // must not depend on the width of the sweep it is part of)
-        push_chain(nst == 1 ? bwd_wg : bmulti, bwd_slabs, fr, t, nst - t + nbt_b, split_level && nst > 1, 0, true);
-    }
-    h_fwd_nsingle[l] = static_cast<int>(fwd_wg.size()) - h_fwd_ptr[l];
-    h_bwd_nsingle[l] = static_cast<int>(bwd_wg.size()) - h_bwd_ptr[l];
-    bwd_wg.insert(bwd_wg.end(), bmulti.begin(), bmulti.end());
-    h_wave_ptr[l + 1] = static_cast<int>(wave_wg.size());
-    fwd_wg.insert(fwd_wg.end(), multi.begin(), multi.end());
-    h_fwd_ptr[l + 1] = static_cast<int>(fwd_wg.size());
-    // v1 written once per level where the row-tile workgroups that would each gather it are more than the chip holds at
-    // two waves per SIMD (512): the pre-assembled form runs three, and drops an index round from every workgroup.  The
-    // shell model's levels of 4000 to 14000: -30 % per launch; the 1 M-dof column's five levels of 552 to 1984: 1.43 ->
-    // 1.36 ms per 32-column sweep (four factors in one process, tools/pre_ab_probe.py).  Below that the extra launch
-    // costs more than the round it saves
-    if (static_cast<int>(multi.size()) >= pre_min_wg)
-      pre_wg.insert(pre_wg.end(), pre_lvl.begin(), pre_lvl.end());
-    h_pre_ptr[l + 1] = static_cast<int>(pre_wg.size());
-    h_bwd_ptr[l + 1] = static_cast<int>(bwd_wg.size());
-  }
-  const int64_t n_slabs = std::max<int64_t>(1, std::max(fwd_slabs, bwd_slabs));
-  const bool has_v1 = !pre_wg.empty();
-  if (has_v1) nplanes += 1;
-  // rows of the caller's block behind every border entry (backward sweep gathers x there)
-  std::vector<int> bout(s.border.size());
-  for (size_t e = 0; e < s.border.size(); ++e) bout[e] = s.perm[s.border[e]];
   size_t free_b = 0, total_b = 0;
   EIGD_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t need = sizeof(double) * (static_cast<size_t>(s.front_doubles) + s.inv_doubles + toff[nf] +
-                                        2 * ftoff[nf] + fm_doubles + bm_doubles + (2 * nplanes + 1) * v_rows * KBMAX +
-                                        n_slabs * TW * KBMAX) +
-                      16 * s.a_src.size() + (size_t(64) << 20);
-  if (need > free_b) {
-    set_error("factor needs %.2f GiB of device memory, %.2f GiB free", need / 1073741824.0, free_b / 1073741824.0);
-    return EIGD_E_HIP;
-  }
+  const SweepPlan plan = plan_sweeps(s, pre_assembly_min_workgroups());
   eigd_factor* f = new eigd_factor();
+  static_cast<SweepTables&>(*f) = plan;
   f->ctx = ctx;
-  f->sym = &h->s;
-  f->h_fwd_ptr = h_fwd_ptr;
-  f->h_fwd_nsingle = h_fwd_nsingle;
-  f->h_pre_ptr = h_pre_ptr;
-  f->has_v1 = has_v1;
-  f->h_lvl_leaf.assign(static_cast<size_t>(s.nlevels), 1);
-  for (int q = 0; q < nf; ++q)
-    if (nchild[q] > 0) f->h_lvl_leaf[s.f_level[q]] = 0;
-  f->h_lvl_two.assign(static_cast<size_t>(s.nlevels), 1);
-  for (int q = 0; q < nf; ++q)
-    if (nchild[q] > 2) f->h_lvl_two[s.f_level[q]] = 0;
-  f->h_bwd_nsingle = h_bwd_nsingle;
-  f->h_bwd_mxbs.assign(static_cast<size_t>(s.nlevels), 0);
-  for (int q = 0; q < nf; ++q)
-    if (s.f_ns[q] > TW && s.f_parent[q] >= 0)
-      f->h_bwd_mxbs[s.f_level[q]] = std::max<int>(f->h_bwd_mxbs[s.f_level[q]], s.f_bs[q]);
-  f->h_fwd_kd.assign(static_cast<size_t>(s.nlevels), 8);
-  f->h_bwd_kd.assign(static_cast<size_t>(s.nlevels), 8);
-  {
-    // levels for the wave-per-block kernels: every single-column-tile front has at most thin_fwd / thin_bwd own
-    // columns and (backward) a border of <= 320
-    constexpr int thin_fwd = TW, thin_bwd = TW;
-    std::vector<int> mxns(static_cast<size_t>(s.nlevels), 0), mxbs(static_cast<size_t>(s.nlevels), 0);
-    for (int q = 0; q < nf; ++q) {
-      if (s.f_ns[q] > TW) continue;
-      mxns[s.f_level[q]] = std::max<int>(mxns[s.f_level[q]], s.f_ns[q]);
-      mxbs[s.f_level[q]] = std::max<int>(mxbs[s.f_level[q]], s.f_bs[q]);
-    }
-    f->h_thin_fwd.assign(static_cast<size_t>(s.nlevels), 0);
-    f->h_thin_bwd.assign(static_cast<size_t>(s.nlevels), 0);
-    for (int l = 0; l < s.nlevels; ++l) {
-      // (fronts with carry planes and 33 to 48 own columns: 12 K-steps -- the buffer-access kernels, several waves per front)
-      const int nks = (mxns[l] <= 16) ? 4 : (mxns[l] <= 32) ? 8 : (mxns[l] <= 48 && !f->h_lvl_leaf[l]) ? 12 : 16;
-      // leaf level: K-steps of the forward kernel cut to the widest front (12 / 14 instead of 16: fewer MFMAs on zeros)
-      const int nks_leaf = (mxns[l] > 32 && mxns[l] <= 48) ? 12 : (mxns[l] > 48 && mxns[l] <= 56) ? 14 : nks;
-      // (with carries to gather, the 16-step forward variant needs 244 VGPRs: those levels stay with the tile kernels)
-      // levels of binary fronts with up to 48 own columns go to the buffer-access thin
-      // kernels too, with two or four waves per front where the level has fewer than 2048 fronts (at C3 the two levels of
-      // 42-column fronts under the multi-tile ones: 61 + 44 us in the tile kernel)
-      const int kids_cap = f->h_lvl_two[l] ? 48 : 32;
-      if (mxns[l] > 0 && mxns[l] <= (f->h_lvl_leaf[l] ? thin_fwd : std::min(thin_fwd, kids_cap)))
-        f->h_thin_fwd[l] = f->h_lvl_leaf[l] ? nks_leaf : nks;
-      // (backward: one wave per front -- with more than 32 own columns only where the level has fronts enough to
-      // fill the chip that way)
-      const int nfl = h_wave_ptr[l + 1] - h_wave_ptr[l];
-      const int nks_b = (mxns[l] <= 16) ? 4 : (mxns[l] <= 32) ? 8 : 16;  // (the backward kernels know 4, 8 and 16 K-steps)
-      if (mxns[l] > 0 && mxns[l] <= thin_bwd && mxbs[l] <= 320 && (nks_b < 16 || nfl >= 1024)) f->h_thin_bwd[l] = nks_b;
-    }
-  }
-  for (int q = 0; q < nf; ++q) {
-    if (s.f_ns[q] > TW) continue;
-    const int l = s.f_level[q];
-    const int bsq = (s.f_parent[q] >= 0) ? std::min<int>(TW, s.f_bs[q]) : 0;
-    f->h_fwd_kd[l] = std::max(f->h_fwd_kd[l], (s.f_ns[q] + 7) & ~7);
-    f->h_bwd_kd[l] = std::max(f->h_bwd_kd[l], (std::max<int>(s.f_ns[q], bsq) + 7) & ~7);
-  }
-  f->h_wave_ptr = h_wave_ptr;
-  f->ft_doubles = ftoff[nf];
-  f->fm_doubles = fm_doubles;
-  f->bm_doubles = bm_doubles;
-  f->n_ff = static_cast<int>(ffr.size());
-  f->n_mt = mt_pref.back();
-  f->n_tr = tr_pref[nf];
-  f->h_bwd_ptr = h_bwd_ptr;
-  f->ov_lvl_ptr = ov_lvl_ptr;
-  f->t_doubles = toff[nf];
-  f->v_rows = v_rows;
-  f->nslot = nslot;
-  f->nplanes = nplanes;
-  f->n_slabs = n_slabs;
-  f->n_tickets = std::max(1, n_tickets);
-  f->n_tri = tri_pref[nf];
-  f->n_m21 = m_pref[nf];
-
-  int rc = EIGD_OK;
-#define UP(dst, vec)                          \
-  if (rc == EIGD_OK) rc = upload(f, &f->dst, vec);
-  UP(d_c0, s.f_c0)
-  UP(d_ns, s.f_ns)
-  UP(d_bs, s.f_bs)
-  UP(d_parent, s.f_parent)
-  UP(d_rel, s.rel)
-  UP(d_foff, s.f_foff)
-  UP(d_voff, s.f_voff)
-  UP(d_ioff, s.f_ioff)
-  UP(d_bptr, s.f_bptr)
-  UP(d_lvl_fronts, s.lvl_fronts)
-  UP(d_pref_chunks, s.pref_chunks)
-  UP(d_pref_tiles, s.pref_tiles)
-  UP(d_fwd_wg, fwd_wg)
-  UP(d_bwd_wg, bwd_wg)
-  UP(d_wave_wg, wave_wg)
-  UP(d_pre_wg, pre_wg)
-  UP(d_ftoff, ftoff)
-  UP(d_tr_pref, tr_pref)
-  UP(d_mt_pref, mt_pref)
-  if (!ffr.empty()) {
-    UP(d_ff, ffr)
-  }
-  UP(d_bout, bout)
-  UP(d_tri_pref, tri_pref)
-  UP(d_m_pref, m_pref)
-  UP(d_toff, toff)
-  UP(d_ov_dst, ov_dst)
-  UP(d_ov_ptr, ov_ptr)
-  UP(d_ov_src, ov_src)
-  UP(d_cs_child, s.cs_child)
-  UP(d_a_src, s.a_src)
-  UP(d_a_dst, s.a_dst)
-  UP(d_v_src, s.v_src)
-  if (lu) {
-    // FU holds the upper triangle transposed: an upper entry goes to the mirror of its place in the front square
-    std::vector<int64_t> fu_dst(s.u_dst.size());
-    for (size_t e = 0; e < s.u_dst.size(); ++e) {
-      const int64_t dst = s.u_dst[e];
-      const int q = static_cast<int>(std::upper_bound(s.f_foff.begin(), s.f_foff.end(), dst) - s.f_foff.begin()) - 1;
-      const int64_t dq = s.f_ns[q] + s.f_bs[q], loc = dst - s.f_foff[q];
-      fu_dst[e] = s.f_foff[q] + (loc % dq) * dq + loc / dq;
-    }
-    UP(d_u_src, s.u_src)
-    UP(d_u_dst, fu_dst)
-    f->nupper = static_cast<int64_t>(s.u_src.size());
-  }
-  {
-    // which carry planes hold a contribution on which row: child number q of a front writes plane q at the parent's
-    // rows rel(border); the summed surplus children arrive in plane nslot - 1
-    std::vector<int> cmask(static_cast<size_t>(s.sumd), 0);
-    for (int c = 0; c < nf; ++c) {
-      const int p = s.f_parent[c];
-      if (p < 0 || s.f_bs[c] == 0) continue;
-      const int bit = (child_no[c] >= kMaxS) ? nslot - 1 : child_no[c];
-      const int64_t b0 = s.f_bptr[c];
-      for (int i = 0; i < s.f_bs[c]; ++i) cmask[static_cast<size_t>(s.f_voff[p] + s.rel[b0 + i])] |= 1 << bit;
-    }
-    UP(d_cmask, cmask)
-  }
-#undef UP
+  f->sym = &s;
+  f->lu = lu;
+  f->L.nmap = s.nlower;
   int64_t maxsrc = 0;
   for (int64_t e : s.a_src) maxsrc = std::max(maxsrc, e);
-  if (lu)
-    for (int64_t e : s.u_src) maxsrc = std::max(maxsrc, e);
-  f->data_len = maxsrc + 1;
-  // the caller's CSR data array may be longer (upper-triangle entries after the last lower one): we copy a prefix
-  auto dmalloc = [&](double** p, size_t count) -> int {
-    if (rc != EIGD_OK) return rc;
-    size_t b = sizeof(double) * std::max<size_t>(count, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), b);
-    if (e != hipSuccess) {
-      set_error("hipMalloc of %.2f GiB failed: %s", b / 1073741824.0, hipGetErrorString(e));
-      return EIGD_E_HIP;
-    }
-    f->bytes += b;
-    return EIGD_OK;
-  };
-  rc = dmalloc(&f->d_data, f->data_len);
-  rc = dmalloc(&f->d_F, s.front_doubles);
-  rc = dmalloc(&f->d_Inv, s.inv_doubles);
-  rc = dmalloc(&f->d_T, static_cast<size_t>(f->t_doubles));
-  rc = dmalloc(&f->d_aux, 2);
-  rc = dmalloc(&f->d_red, 512);
-  rc = dmalloc(&f->d_Ft, static_cast<size_t>(f->ft_doubles));
-  rc = dmalloc(&f->d_Fb, static_cast<size_t>(f->ft_doubles));
-  rc = dmalloc(&f->d_Fm, static_cast<size_t>(std::max<int64_t>(f->fm_doubles, 1)));
-  rc = dmalloc(&f->d_Bm, static_cast<size_t>(std::max<int64_t>(f->bm_doubles, 1)));
-  rc = dmalloc(&f->d_P, static_cast<size_t>(n_slabs) * TW * KBMAX);
-  if (rc == EIGD_OK) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_tickets), sizeof(int) * f->n_tickets);
-    if (e != hipSuccess) {
-      set_error("hipMalloc failed: %s", hipGetErrorString(e));
-      rc = EIGD_E_HIP;
-    } else {
-      e = hipMemset(f->d_tickets, 0, sizeof(int) * f->n_tickets);
-    }
-  }
-  rc = dmalloc(&f->d_V, static_cast<size_t>(nplanes) * v_rows * kPlaneCols);
-  rc = dmalloc(&f->d_Y, static_cast<size_t>(s.sumd) * KBMAX);
-  rc = dmalloc(&f->d_sgn, static_cast<size_t>(s.n));
-  if (lu) {  // the U side
-    rc = dmalloc(&f->d_FU, s.front_doubles);
-    rc = dmalloc(&f->d_InvU, s.inv_doubles);
-    rc = dmalloc(&f->d_TU, static_cast<size_t>(f->t_doubles));
-    rc = dmalloc(&f->d_FtU, static_cast<size_t>(f->ft_doubles));
-    rc = dmalloc(&f->d_BmU, static_cast<size_t>(std::max<int64_t>(f->bm_doubles, 1)));
-  }
-  if (rc == EIGD_OK) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_flag), 4 * sizeof(int));
-    if (e != hipSuccess) {
-      set_error("hipMalloc failed: %s", hipGetErrorString(e));
-      rc = EIGD_E_HIP;
-    }
-  }
-  if (rc != EIGD_OK) {
-    eigd_factor_free(f);
-    return rc;
-  }
-  // extend-add launch shapes
-  f->ea_split.assign(static_cast<size_t>(s.nlevels) * s.maxslots, 1);
-  for (size_t rec = 0; rec + 1 < s.cs_ptr.size(); ++rec) {
-    int64_t maxbs = 1;
-    for (int q = s.cs_ptr[rec]; q < s.cs_ptr[rec + 1]; ++q) maxbs = std::max<int64_t>(maxbs, s.f_bs[s.cs_child[q]]);
-    int64_t split = (maxbs * maxbs + kThreads * 32 - 1) / (kThreads * 32);
-    f->ea_split[rec] = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(split, 512)));
-  }
-  EIGD_HIP(hipMemsetAsync(f->d_Inv, 0, sizeof(double) * std::max<int64_t>(s.inv_doubles, 1), ctx->stream));
-  EIGD_HIP(hipMemsetAsync(f->d_T, 0, sizeof(double) * std::max<int64_t>(f->t_doubles, 1), ctx->stream));  // upper triangles stay zero
   if (lu) {
-    EIGD_HIP(hipMemsetAsync(f->d_InvU, 0, sizeof(double) * std::max<int64_t>(s.inv_doubles, 1), ctx->stream));
-    EIGD_HIP(hipMemsetAsync(f->d_TU, 0, sizeof(double) * std::max<int64_t>(f->t_doubles, 1), ctx->stream));
+    f->U.nmap = static_cast<int64_t>(s.u_src.size());
+    for (int64_t e : s.u_src) maxsrc = std::max(maxsrc, e);
   }
-  f->lu = lu;
-  // carry planes: entries no child writes must read as zero, in every sweep
-  EIGD_HIP(hipMemsetAsync(f->d_V, 0, sizeof(double) * std::max<int64_t>(static_cast<int64_t>(nplanes) * v_rows * kPlaneCols, 1),
-                          ctx->stream));
-  {
-    double aux[2] = {0.0, 0.0};
-    const int m1 = -1;
-    std::memcpy(&aux[1], &m1, sizeof(int));
-    EIGD_HIP(hipMemcpy(f->d_aux, aux, sizeof(aux), hipMemcpyHostToDevice));
+  // the caller's CSR data array may be longer (upper-triangle entries after the last lower one): we copy a prefix
+  f->data_len = maxsrc + 1;
+  f->bufs = factor_buffers(f, plan);
+  size_t need = size_t(64) << 20;
+  for (const DeviceBuffer& b : f->bufs) need += b.bytes();
+  if (need > free_b) {
+    set_error("factor needs %.2f GiB of device memory, %.2f GiB free", need / 1073741824.0, free_b / 1073741824.0);
+    delete f;
+    return EIGD_E_HIP;
   }
-  rc = numeric(f, hdata);
+  int rc = allocate(f->bufs, ctx->stream, f->bytes);
+  if (rc == EIGD_OK) rc = numeric(f, hdata);
   if (rc != EIGD_OK) {
     eigd_factor_free(f);
     return rc;
@@ -3458,11 +3393,11 @@ int eigd_factor_solve(eigd_factor* f, double* dX, int ldx, int k, double alpha) 
   return eigd_factor_solve_to(f, dX, ldx, dX, ldx, k, alpha);
 }
 
-static int solve_blocks(eigd_factor* f, hipStream_t st, double* wV, double* wY, double* wP, int* wT, const double* dIn,
-                        int ldin, double* dOut, int ldout, int k, double alpha, SweepRecord& record) {
+static int solve_blocks(eigd_factor* f, hipStream_t st, SweepWorkspace& ws, const double* dIn, int ldin, double* dOut,
+                        int ldout, int k, double alpha) {
   EIGD_REQUIRE(f && dIn && dOut, "null argument");
   EIGD_REQUIRE(k >= 1 && ldin >= k && ldout >= k, "bad block shape k=%d ldin=%d ldout=%d", k, ldin, ldout);
-  SweepRecord* rec = f->record_sweeps ? &record : nullptr;
+  SweepRecord* rec = f->record_sweeps ? &ws.rec : nullptr;
   if (rec) rec->launches.clear();
   const SweepCopies cp = f->copies();
   for (int c0 = 0; c0 < k; c0 += KBMAX) {
@@ -3470,11 +3405,11 @@ static int solve_blocks(eigd_factor* f, hipStream_t st, double* wV, double* wY, 
     int rc;
     // 5 to 8 columns go through the 16-column kernels, whose single-tile levels are MFMA wave kernels (1.26 -> 1.09 ms)
     if (kb <= 4)
-      rc = sweep<1>(f, cp, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+      rc = sweep<1>(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     else if (kb <= 16)
-      rc = sweep<4>(f, cp, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+      rc = sweep<4>(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     else
-      rc = sweep<8>(f, cp, st, wV, wY, wP, wT, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+      rc = sweep<8>(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     if (rc != EIGD_OK) return rc;
   }
   return EIGD_OK;
@@ -3482,39 +3417,22 @@ static int solve_blocks(eigd_factor* f, hipStream_t st, double* wV, double* wY, 
 
 int eigd_factor_solve_to(eigd_factor* f, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha) {
   EIGD_REQUIRE(f, "null argument");
-  return solve_blocks(f, f->ctx->stream, f->d_V, f->d_Y, f->d_P, f->d_tickets, dIn, ldin, dOut, ldout, k, alpha, f->rec);
+  return solve_blocks(f, f->ctx->stream, f->ws, dIn, ldin, dOut, ldout, k, alpha);
 }
-
-// A lane = a second set of sweep workspaces bound to another context (stream) of the same device: sweeps of
-// different lanes run concurrently on the one factor (independent mode groups overlap each other's latency).
-struct eigd_lane {
-  eigd_factor* f = nullptr;
-  eigd_ctx* ctx = nullptr;
-  double *V = nullptr, *Y = nullptr, *P = nullptr;
-  int* tickets = nullptr;
-  SweepRecord rec;  // launches of the lane's most recent solve (when its factor records them)
-};
 
 int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out) {
   EIGD_REQUIRE(f && ctx && out, "null argument");
   EIGD_REQUIRE(ctx->device == f->ctx->device, "lane context must live on the factor's device");
   *out = nullptr;
-  const Symbolic& s = *f->sym;
   eigd_lane* l = new eigd_lane();
   l->f = f;
   l->ctx = ctx;
-  const size_t vb = sizeof(double) * std::max<size_t>(static_cast<size_t>(f->nplanes) * f->v_rows * kPlaneCols, 1);
-  const size_t yb = sizeof(double) * std::max<size_t>(static_cast<size_t>(s.sumd) * KBMAX, 1);
-  hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&l->V), vb);
-  hipError_t e2 = hipMalloc(reinterpret_cast<void**>(&l->Y), yb);
-  hipError_t e3 = hipMalloc(reinterpret_cast<void**>(&l->P), sizeof(double) * static_cast<size_t>(f->n_slabs) * TW * KBMAX);
-  hipError_t e4 = hipMalloc(reinterpret_cast<void**>(&l->tickets), sizeof(int) * f->n_tickets);
-  if (e4 == hipSuccess) e4 = hipMemset(l->tickets, 0, sizeof(int) * f->n_tickets);
-  if (e1 == hipSuccess) e1 = hipMemset(l->V, 0, vb);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
+  l->bufs = workspace_buffers(l->ws, *f);
+  size_t bytes = 0;
+  const int rc = allocate(l->bufs, ctx->stream, bytes);  // (zeroed on the lane's own stream)
+  if (rc != EIGD_OK) {
     eigd_factor_lane_free(l);
-    set_error("hipMalloc failed for a sweep lane");
-    return EIGD_E_HIP;
+    return rc;
   }
   *out = l;
   return EIGD_OK;
@@ -3523,17 +3441,14 @@ int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out) {
 int eigd_factor_lane_free(eigd_lane* l) {
   if (!l) return EIGD_OK;
   if (l->ctx && l->ctx->stream) (void)hipStreamSynchronize(l->ctx->stream);
-  if (l->V) (void)hipFree(l->V);
-  if (l->Y) (void)hipFree(l->Y);
-  if (l->P) (void)hipFree(l->P);
-  if (l->tickets) (void)hipFree(l->tickets);
+  release(l->bufs);
   delete l;
   return EIGD_OK;
 }
 
 int eigd_factor_lane_solve_to(eigd_lane* l, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha) {
   EIGD_REQUIRE(l, "null argument");
-  return solve_blocks(l->f, l->ctx->stream, l->V, l->Y, l->P, l->tickets, dIn, ldin, dOut, ldout, k, alpha, l->rec);
+  return solve_blocks(l->f, l->ctx->stream, l->ws, dIn, ldin, dOut, ldout, k, alpha);
 }
 
 int eigd_sweep_variants(const char** names, int cap, int* count) {
@@ -3553,7 +3468,7 @@ int eigd_factor_record_sweeps(eigd_factor* f, int on) {
 int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int* level, int* kb, int cap, int* count) {
   EIGD_REQUIRE(f && count && (cap <= 0 || (variant && level && kb)), "null argument");
   EIGD_REQUIRE(!lane || lane->f == f, "the lane belongs to another factor");
-  const std::vector<SweepLaunch>& r = (lane ? lane->rec : f->rec).launches;
+  const std::vector<SweepLaunch>& r = (lane ? lane->ws : f->ws).rec.launches;
   *count = static_cast<int>(r.size());
   for (int i = 0; i < cap && i < *count; ++i) {
     variant[i] = r[static_cast<size_t>(i)].variant;

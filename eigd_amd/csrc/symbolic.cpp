@@ -746,7 +746,7 @@ bool build_upper_map(Symbolic& s) {
     lower_lo[r] = std::min(lower_lo[r], e);
     lower_hi[r] = std::max(lower_hi[r], e);
     if (ni != nj) {
-      up.push_back(Up{c, r, s.f_foff[f] + lr * d + lc});  // mirror of the lower place: row lc, column lr
+      up.push_back(Up{c, r, dst});  // FU holds the upper triangle transposed: the lower place of (r, c)
       cnt[c + 1]++;
     }
   }

@@ -46,8 +46,8 @@ struct Symbolic {
   int64_t nlower = 0;
   int64_t nnz = 0;  // entries of the analysed pattern
   std::vector<int64_t> a_src, a_dst;
-  // scatter of the strictly upper entries (LU factors only, build_upper_map): u_dst is the mirror, inside the same
-  // front, of the lower destination the transposed entry would get (own row of the entry's row, place of its column)
+  // scatter of the strictly upper entries (LU factors only, build_upper_map) into the front buffer of the transposed
+  // upper triangles: u_dst is the lower destination the transposed entry would get (a_dst of its mirror)
   bool has_upper = false;
   std::vector<int64_t> u_src, u_dst;
   // source row (original numbering) of every front-vector row, -1 for border rows

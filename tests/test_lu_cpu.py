@@ -44,7 +44,8 @@ def test_upper_and_lower_maps_cover_every_entry_once():
         np.testing.assert_array_equal(src, np.arange(pattern.nnz))
 
 
-def test_upper_destination_mirrors_the_transposed_lower_one():
+def test_upper_destination_is_the_transposed_lower_one():
+    """the upper triangle is kept transposed (FU): an upper entry goes where its transpose goes in the lower fronts"""
     A = symmetrised_pattern(unsymmetric_pattern(seed=3))
     sym = Symbolic(A, leaf_size=16)
     ns, bs, foff = sym.array("f_ns"), sym.array("f_bs"), sym.array("f_foff")
@@ -59,14 +60,15 @@ def test_upper_destination_mirrors_the_transposed_lower_one():
     for e, d in zip(u_src, u_dst):
         t = lower[(int(cols[e]), int(rows[e]))]                 # where the transposed entry goes
         f = front_of(foff, t)
-        assert front_of(foff, d) == f                           # same front
         dq = int(ns[f] + bs[f])
         loc = t - foff[f]
         i, j = loc % dq, loc // dq                              # (row, column) of the transposed entry's place
         assert j < ns[f] and i >= j
-        assert d == foff[f] + i * dq + j                        # ... mirrored: (j, i)
-    # every destination is distinct and inside the fronts
-    assert len(np.unique(np.concatenate([a_dst, u_dst]))) == A.nnz
+        assert d == t
+    # within each buffer (F: a_dst, FU: u_dst) every destination is distinct, and the two cover every entry once
+    assert len(np.unique(a_dst)) == len(a_dst)
+    assert len(np.unique(u_dst)) == len(u_dst)
+    assert len(a_dst) + len(u_dst) == A.nnz
     assert u_dst.min() >= 0 and u_dst.max() < sym.sizes["front_doubles"]
 
 
