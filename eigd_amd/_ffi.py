@@ -62,6 +62,7 @@ _SIGNATURES = {
     "eigd_symbolic_create_geom": [c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, P(c_vp)],
     "eigd_symbolic_free": [c_vp],
     "eigd_symbolic_sizes": [c_vp, c_vp, c_int],
+    "eigd_symbolic_sweep_plan": [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, P(c_int)],
     "eigd_symbolic_get_i32": [c_vp, C.c_char_p, c_vp, c_i64],
     "eigd_symbolic_get_i64": [c_vp, C.c_char_p, c_vp, c_i64],
     "eigd_factor_create": [c_vp, c_vp, c_vp, P(c_vp)],

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <tuple>
 
 #include "common.h"
 #include "symbolic.h"
@@ -2188,47 +2189,127 @@ __global__ __launch_bounds__(kThreads) void pack_frag_kernel(FrontArrays fa, con
   }
 }
 
-// ------------------------------------------------------------------ launch record of the sweeps
-// Every launch of sweep() goes through EIGD_SWEEP_LAUNCH, which names the kernel with its resolved template arguments
-// the way a kernel trace prints them ("fwd_thin_kernel<32, 12, 2, 2, true>").  Each launch site registers that name
-// when the library is loaded (static member of SweepVariant, instantiated by the site), so the table is exactly the
-// set of variants the compiled sweeps can launch, unreachable arms included.  A solver object with recording on
-// appends (variant, level, columns) of every launch of its most recent solve; off, a launch costs one branch.
-inline std::vector<std::string>& sweep_variant_table() {
-  static std::vector<std::string> t;
-  return t;
-}
+// ------------------------------------------------------------------ kernel table and launch record of the sweeps
+// sweep_kernels() is the one list of the sweep kernels' instantiations: a kernel that is not in it is not compiled.
+// An entry is named with its template arguments the way a kernel trace prints them ("fwd_thin_kernel<32, 12, 2, 2,
+// true>", defaults spelled out); its index is the variant id of plans and launch records.  The launch policy
+// (sweep_launches) asks for entries by family and template arguments; the launcher (sweep) calls them.  A solver object
+// with recording on appends (variant, level, columns) of every launch of its most recent solve.
+enum SweepFamily {  // (in the order of kSweepFamilyName and SweepFns)
+  overflow_sum_kernel_family, fwd_wave_kernel_family, fwd_thin_kernel_family, fwd_level_kernel_family,
+  v1_assemble_kernel_family, bwd_level_kernel_family, bwd_wave_kernel_family, bwd_thin_kernel_family
+};
+constexpr const char* kSweepFamilyName[] = {"overflow_sum_kernel", "fwd_wave_kernel", "fwd_thin_kernel", "fwd_level_kernel",
+                                            "v1_assemble_kernel", "bwd_level_kernel", "bwd_wave_kernel", "bwd_thin_kernel"};
+// the kernels of a family share one argument list: the type of any of its instantiations
+using SweepFns = std::tuple<decltype(&overflow_sum_kernel), decltype(&fwd_wave_kernel<4, 0, 2>),
+                            decltype(&fwd_thin_kernel<16, 4, 0, 1, true>), decltype(&fwd_level_kernel<1, false, 2>),
+                            decltype(&v1_assemble_kernel<4, 2>), decltype(&bwd_level_kernel<1, false>),
+                            decltype(&bwd_wave_kernel<4>), decltype(&bwd_thin_kernel<16, 1, 8, true>)>;
+template <SweepFamily FAM>
+using SweepFn = std::tuple_element_t<FAM, SweepFns>;
+
+constexpr int kSweepTargs = 5;
+struct SweepKernel {
+  SweepFamily family;
+  int targ[kSweepTargs];  // template arguments (bool: 0 / 1), zero-filled
+  void (*fn)();           // a SweepFn<family>
+  std::string name;
+  template <SweepFamily FAM>
+  SweepFn<FAM> as() const { return reinterpret_cast<SweepFn<FAM>>(fn); }
+};
 inline std::string sweep_targ(int v) { return std::to_string(v); }
 inline std::string sweep_targ(bool v) { return v ? "true" : "false"; }
-template <typename... A>
-int register_sweep_variant(const char* family, A... a) {
-  std::string name = family;
+template <SweepFamily FAM, auto... A>
+SweepKernel sweep_kernel(SweepFn<FAM> fn) {
+  static_assert(sizeof...(A) <= kSweepTargs);
+  std::string name = kSweepFamilyName[FAM];
   if constexpr (sizeof...(A) > 0) {
     const char* sep = "<";
-    ((name += sep, name += sweep_targ(a), sep = ", "), ...);
+    ((name += sep, name += sweep_targ(A), sep = ", "), ...);
     name += ">";
   }
-  std::vector<std::string>& t = sweep_variant_table();
-  for (size_t i = 0; i < t.size(); ++i)
-    if (t[i] == name) return static_cast<int>(i);  // (two arms of the dispatch may launch one instantiation)
-  t.push_back(name);
-  return static_cast<int>(t.size()) - 1;
+  return {FAM, {static_cast<int>(A)...}, reinterpret_cast<void (*)()>(fn), name};
 }
-template <const char* FAM, auto... A>
-struct SweepVariant {
-  static const int id;
-};
-template <const char* FAM, auto... A>
-const int SweepVariant<FAM, A...>::id = register_sweep_variant(FAM, A...);
-constexpr char fwd_wave_kernel_family[] = "fwd_wave_kernel";
-constexpr char bwd_wave_kernel_family[] = "bwd_wave_kernel";
-constexpr char fwd_thin_kernel_family[] = "fwd_thin_kernel";
-constexpr char bwd_thin_kernel_family[] = "bwd_thin_kernel";
-constexpr char fwd_level_kernel_family[] = "fwd_level_kernel";
-constexpr char bwd_level_kernel_family[] = "bwd_level_kernel";
-constexpr char v1_assemble_kernel_family[] = "v1_assemble_kernel";
-constexpr char overflow_sum_kernel_family[] = "overflow_sum_kernel";
+#define EIGD_SWEEP_KERNEL(KERNEL, ...) sweep_kernel<KERNEL##_family, __VA_ARGS__>(KERNEL<__VA_ARGS__>)
 
+// the wave-per-block kernels of one sweep width and factor kind (TRI: triangular diagonal blocks, Cholesky and LU)
+template <int KB, bool TRI>
+void add_thin_kernels(std::vector<SweepKernel>& t) {
+  t.insert(t.end(), {EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 4, 0, 1, TRI),  // leaves: K-steps cut to the widest front
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 8, 0, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 12, 0, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 14, 0, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 16, 0, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 4, 2, 1, TRI),  // up to 32 own columns with carries
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 4, kMaxS + 1, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 8, 2, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 8, kMaxS + 1, 1, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 12, 2, 1, TRI),  // binary fronts of 33 to 48 own columns
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 12, 2, 2, TRI),
+                     EIGD_SWEEP_KERNEL(fwd_thin_kernel, KB, 12, 2, 4, TRI),
+                     EIGD_SWEEP_KERNEL(bwd_thin_kernel, KB, 1, 8, TRI),
+                     EIGD_SWEEP_KERNEL(bwd_thin_kernel, KB, 2, 8, TRI),
+                     EIGD_SWEEP_KERNEL(bwd_thin_kernel, KB, 4, 4, TRI)});
+}
+// the tile kernels of the MFMA widths (16 and 32 columns)
+template <int KPT>
+void add_mfma_level_kernels(std::vector<SweepKernel>& t) {
+  t.insert(t.end(), {EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, true, 0, false, false),  // single column tile
+                     EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, true, 2, false, false),
+                     EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, true, kMaxS + 1, false, false),
+                     EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, false, 2, true, false),  // several: fragment-major operands
+                     EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, false, kMaxS + 1, true, false),
+                     EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, false, 2, true, true),   // ... v1 pre-assembled
+                     EIGD_SWEEP_KERNEL(fwd_level_kernel, KPT, false, kMaxS + 1, true, true),
+                     EIGD_SWEEP_KERNEL(v1_assemble_kernel, KPT, 2),
+                     EIGD_SWEEP_KERNEL(v1_assemble_kernel, KPT, kMaxS + 1),
+                     EIGD_SWEEP_KERNEL(bwd_level_kernel, KPT, true, false, false),
+                     EIGD_SWEEP_KERNEL(bwd_level_kernel, KPT, false, true, false)});
+}
+inline const std::vector<SweepKernel>& sweep_kernels() {
+  static const std::vector<SweepKernel> table = [] {
+    std::vector<SweepKernel> t = {
+        sweep_kernel<overflow_sum_kernel_family>(overflow_sum_kernel),
+        // 4 columns: the single-tile fronts wave by wave, the others through the vector-FMA tile kernels
+        EIGD_SWEEP_KERNEL(fwd_wave_kernel, 4, 0, 2),
+        EIGD_SWEEP_KERNEL(fwd_wave_kernel, 4, 2, 2),
+        EIGD_SWEEP_KERNEL(fwd_wave_kernel, 4, kMaxS + 1, 2),
+        EIGD_SWEEP_KERNEL(bwd_wave_kernel, 4),
+        EIGD_SWEEP_KERNEL(fwd_level_kernel, 1, false, 2, false, false),
+        EIGD_SWEEP_KERNEL(fwd_level_kernel, 1, false, kMaxS + 1, false, false),
+        EIGD_SWEEP_KERNEL(bwd_level_kernel, 1, false, false, false),
+        EIGD_SWEEP_KERNEL(bwd_level_kernel, 8, false, true, true)};  // (border index list in LDS)
+    add_mfma_level_kernels<4>(t);
+    add_mfma_level_kernels<8>(t);
+    add_thin_kernels<16, true>(t);
+    add_thin_kernels<16, false>(t);
+    add_thin_kernels<32, true>(t);
+    add_thin_kernels<32, false>(t);
+    return t;
+  }();
+  return table;
+}
+#undef EIGD_SWEEP_KERNEL
+inline int find_sweep_kernel(SweepFamily family, const int (&targ)[kSweepTargs]) {
+  const std::vector<SweepKernel>& t = sweep_kernels();
+  for (size_t i = 0; i < t.size(); ++i)
+    if (t[i].family == family && std::equal(targ, targ + kSweepTargs, t[i].targ)) return static_cast<int>(i);
+  return -1;
+}
+
+// One planned launch of a sweep (sweep_launches): which kernel, at which level, with which geometry, on which records
+struct PlannedLaunch {
+  SweepFamily family;
+  int targ[kSweepTargs];
+  int variant;     // index into sweep_kernels(); -1: the table lacks what the policy asks for
+  int level;
+  int grid, block;  // workgroups, threads
+  unsigned lds;     // dynamic LDS bytes
+  int first;       // first record of the array the family reads (wave_wg, fwd_wg, bwd_wg, pre_wg; overflow rows)
+  int kd, nwg, per_xcd;  // LevelArgs of the tile kernels (overflow_sum: nwg rows, grid = one thread per row and column)
+  bool frag;       // tile kernels: the matrix operands come from the fragment-major copies (Fm, Bm)
+};
 struct SweepLaunch {
   int variant, level, kb;
 };
@@ -2278,7 +2359,7 @@ DeviceBuffer upload_buffer(const char* name, T*& p, const std::vector<T>& h) {
 // Host planning of the sweeps and of the copy kernels (plan_sweeps): what the factor keeps ...
 struct SweepTables {
   std::vector<int> h_fwd_ptr, h_bwd_ptr;  // per level: first workgroup record
-  std::vector<int> h_thin_fwd, h_thin_bwd;  // per level: 4, 8 or 16 K-steps (of 4 own columns) of the wave-per-block kernels, 0: the tile kernels
+  std::vector<int> h_thin_ns, h_thin_bs;  // per level, single-column-tile fronts: most own columns, longest border
   std::vector<int> h_fwd_kd, h_bwd_kd;    // per level: LDS tile rows of the single-column-tile launches (multiple of 8)
   std::vector<char> h_lvl_two;            // per level: every front has at most two children (two-plane kernels)
   std::vector<char> h_lvl_leaf;           // per level: no front has children (kernels without carry loads)
@@ -2343,6 +2424,9 @@ struct eigd_factor : SweepTables {
   // L side; an LU factor of an unsymmetric matrix (eigd_factor_create_lu) has a U side too: the sweeps read forward
   // the L side, backward the U side.  Fb and Fm are forward copies: the L side's
   FactorSide L, U;
+  // what a sweep launches (sweep_launches), per [width class][tri][thin_buf]: built once when the factor is created, so
+  // that a solve walks a list and allocates nothing, and a hole in the kernel table fails the creation
+  std::vector<PlannedLaunch> launches[3][2][2];
   SweepWorkspace ws;                // of the factor's own stream
   std::vector<DeviceBuffer> bufs;   // every device array above
   size_t bytes = 0;
@@ -2834,40 +2918,13 @@ SweepPlan plan_sweeps(const Symbolic& s, int pre_min_wg) {
       p.h_bwd_mxbs[s.f_level[q]] = std::max<int>(p.h_bwd_mxbs[s.f_level[q]], s.f_bs[q]);
   p.h_fwd_kd.assign(static_cast<size_t>(s.nlevels), 8);
   p.h_bwd_kd.assign(static_cast<size_t>(s.nlevels), 8);
-  {
-    // levels for the wave-per-block kernels: every single-column-tile front has at most thin_fwd / thin_bwd own
-    // columns and (backward) a border of <= 320
-    constexpr int thin_fwd = TW, thin_bwd = TW;
-    std::vector<int> mxns(static_cast<size_t>(s.nlevels), 0), mxbs(static_cast<size_t>(s.nlevels), 0);
-    for (int q = 0; q < nf; ++q) {
-      if (s.f_ns[q] > TW) continue;
-      mxns[s.f_level[q]] = std::max<int>(mxns[s.f_level[q]], s.f_ns[q]);
-      mxbs[s.f_level[q]] = std::max<int>(mxbs[s.f_level[q]], s.f_bs[q]);
-    }
-    p.h_thin_fwd.assign(static_cast<size_t>(s.nlevels), 0);
-    p.h_thin_bwd.assign(static_cast<size_t>(s.nlevels), 0);
-    for (int l = 0; l < s.nlevels; ++l) {
-      // (fronts with carry planes and 33 to 48 own columns: 12 K-steps -- the buffer-access kernels, several waves per front)
-      const int nks = (mxns[l] <= 16) ? 4 : (mxns[l] <= 32) ? 8 : (mxns[l] <= 48 && !p.h_lvl_leaf[l]) ? 12 : 16;
-      // leaf level: K-steps of the forward kernel cut to the widest front (12 / 14 instead of 16: fewer MFMAs on zeros)
-      const int nks_leaf = (mxns[l] > 32 && mxns[l] <= 48) ? 12 : (mxns[l] > 48 && mxns[l] <= 56) ? 14 : nks;
-      // (with carries to gather, the 16-step forward variant needs 244 VGPRs: those levels stay with the tile kernels)
-      // levels of binary fronts with up to 48 own columns go to the buffer-access thin
-      // kernels too, with two or four waves per front where the level has fewer than 2048 fronts (at C3 the two levels of
-      // 42-column fronts under the multi-tile ones: 61 + 44 us in the tile kernel)
-      const int kids_cap = p.h_lvl_two[l] ? 48 : 32;
-      if (mxns[l] > 0 && mxns[l] <= (p.h_lvl_leaf[l] ? thin_fwd : std::min(thin_fwd, kids_cap)))
-        p.h_thin_fwd[l] = p.h_lvl_leaf[l] ? nks_leaf : nks;
-      // (backward: one wave per front -- with more than 32 own columns only where the level has fronts enough to
-      // fill the chip that way)
-      const int nfl = p.h_wave_ptr[l + 1] - p.h_wave_ptr[l];
-      const int nks_b = (mxns[l] <= 16) ? 4 : (mxns[l] <= 32) ? 8 : 16;  // (the backward kernels know 4, 8 and 16 K-steps)
-      if (mxns[l] > 0 && mxns[l] <= thin_bwd && mxbs[l] <= 320 && (nks_b < 16 || nfl >= 1024)) p.h_thin_bwd[l] = nks_b;
-    }
-  }
+  p.h_thin_ns.assign(static_cast<size_t>(s.nlevels), 0);  // (which kernels they select: sweep_launches)
+  p.h_thin_bs.assign(static_cast<size_t>(s.nlevels), 0);
   for (int q = 0; q < nf; ++q) {
     if (s.f_ns[q] > TW) continue;
     const int l = s.f_level[q];
+    p.h_thin_ns[l] = std::max<int>(p.h_thin_ns[l], s.f_ns[q]);
+    p.h_thin_bs[l] = std::max<int>(p.h_thin_bs[l], s.f_bs[q]);
     const int bsq = (s.f_parent[q] >= 0) ? std::min<int>(TW, s.f_bs[q]) : 0;
     p.h_fwd_kd[l] = std::max(p.h_fwd_kd[l], (s.f_ns[q] + 7) & ~7);
     p.h_bwd_kd[l] = std::max(p.h_bwd_kd[l], (std::max<int>(s.f_ns[q], bsq) + 7) & ~7);
@@ -2966,256 +3023,179 @@ std::vector<DeviceBuffer> factor_buffers(eigd_factor* f, const SweepPlan& p) {
 
 // Launch policy of the sweeps (all measured on the 1 M-dof benchmark; the experiments behind each number are in
 // docs/LOG.md).  Sweeps of up to 8 columns run their single-tile fronts wave by wave (VALU, readlane broadcast); 5 to 8
-// columns otherwise go through the 16-column MFMA kernels.
+// columns otherwise go through the 16-column MFMA kernels, whose single-tile levels are MFMA wave kernels (1.26 -> 1.09 ms).
 constexpr int kWaveMaxKpt = 2;   // widest sweep (units of 4 columns) whose single-tile fronts use the readlane wave kernels
+inline int sweep_kpt(int kb) { return kb <= 4 ? 1 : kb <= 16 ? 4 : 8; }  // width class of a block of kb columns
 
-// one launch of the sweep: KERNEL<TARGS...> (every template argument spelled out, defaults included: they are part of
-// the variant's name), recorded at level l with kb columns when rec is set
-#define EIGD_UNPAREN(...) __VA_ARGS__
-#define EIGD_SWEEP_LAUNCH(KERNEL, TARGS, ...)                                                               \
-  do {                                                                                                      \
-    if (rec) rec->launches.push_back({SweepVariant<KERNEL##_family, EIGD_UNPAREN TARGS>::id, l, kb});      \
-    hipLaunchKernelGGL((KERNEL<EIGD_UNPAREN TARGS>), __VA_ARGS__);                                         \
-  } while (0)
+// Forward wave-per-block kernel of a level whose widest single-tile front has ns (<= TW) own columns: K-steps of 4 own
+// columns and waves per front; false: the level stays with the tile kernels
+bool thin_fwd_shape(int ns, bool leaf, bool two, int nfronts, int& nks, int& wpf) {
+  wpf = 1;
+  // leaf level: K-steps cut to the widest front (12 / 14 instead of 16: fewer MFMAs on zeros)
+  nks = (ns <= 16) ? 4 : (ns <= 32) ? 8 : (ns <= 48) ? 12 : (ns <= 56) ? 14 : 16;
+  if (leaf || ns <= 32) return true;
+  // (with carries to gather, the 16-step forward variant needs 244 VGPRs: those levels stay with the tile kernels, and
+  // so do fronts of more than 32 own columns with more than two children)
+  if (!two || ns > 48) return false;
+  // binary fronts of 33 to 48 own columns: as many waves per front as give the level >= 2048 waves (at C3 the two
+  // levels of 42-column fronts under the multi-tile ones: 61 + 44 us in the tile kernel)
+  wpf = (nfronts >= 2048) ? 1 : (nfronts >= 1024) ? 2 : 4;
+  return true;
+}
+// Backward: one wave per front and NOB blocks of 16 rows per step (CH: chunk) -- with more than 32 own columns only
+// where the level has fronts enough to fill the chip that way, and borders of at most 320 rows
+bool thin_bwd_shape(int ns, int bs, int nfronts, int& nob, int& ch) {
+  nob = (ns <= 16) ? 1 : (ns <= 32) ? 2 : 4;
+  ch = (ns <= 32) ? 8 : 4;
+  return bs <= 320 && (ns <= 32 || nfronts >= 1024);
+}
 
-template <int KPT>
+// What a sweep of 4 * kpt columns launches, forward then backward, in launch order: every decision between the plan's
+// tables and a launch is made here, from host tables alone (no device, no factor), so it can be queried and tested
+// without a GPU (eigd_symbolic_sweep_plan).  tri: triangular diagonal blocks (false after a Bunch-Kaufman numeric
+// phase); thin_buf: the caller's block ends below 4 GB.  A kernel the table lacks leaves variant = -1.
+std::vector<PlannedLaunch> sweep_launches(const SweepTables& t, int nlevels, int kpt, bool tri, bool thin_buf) {
+  const int KB = 4 * kpt;
+  const int bld = (kpt == 8) ? Tile<8>::BLD : (kpt == 4) ? Tile<4>::BLD : Tile<1>::BLD;
+  const bool mfma = kpt >= 4, wave = kpt <= kWaveMaxKpt;
+  // raw buffer accesses take 32-bit byte offsets: a carry plane and the caller's block must stay below 4 GB, else the
+  // single-tile fronts of the MFMA widths go through the tile kernels
+  const bool thin_ok = mfma && thin_buf && t.v_rows * static_cast<int64_t>(KB) * 8 <= kBufMax;
+  // LDS of the tile kernels: kd + 1 rows of the vector block, with the matrix tile beside it where it is staged.  Fronts
+  // with several column tiles, MFMA widths: matrix operands straight from the fragment-major copies
+  auto lds_tiles = [&](int kd, bool matrix) {
+    return static_cast<unsigned>(sizeof(double) * (kd + 1) * ((matrix ? TLD : 0) + bld));
+  };
+  const unsigned lds_frag = lds_tiles(TW, false);
+  std::vector<PlannedLaunch> out;
+  auto add = [&](int level, SweepFamily family, std::initializer_list<int> targ, int grid, int block, unsigned lds,
+                 int first) -> PlannedLaunch& {
+    out.push_back({family, {}, -1, level, grid, block, lds, first, TW, 0, 0, false});
+    PlannedLaunch& L = out.back();
+    std::copy(targ.begin(), targ.end(), L.targ);
+    L.variant = find_sweep_kernel(family, L.targ);
+    return L;
+  };
+  // tile kernels.  Multi-tile levels: every XCD gets a contiguous range of the level's nwg records (see xcd_record)
+  auto add_tiles = [&](int level, SweepFamily family, std::initializer_list<int> targ, unsigned lds, int first, int nwg,
+                       int kd, bool multi, bool frag) {
+    const int per_xcd = (nwg + 7) / 8;
+    PlannedLaunch& L = add(level, family, targ, multi ? 8 * per_xcd : nwg, kThreads, lds, first);
+    L.kd = kd;
+    L.frag = frag;
+    if (multi) L.nwg = nwg, L.per_xcd = per_xcd;
+  };
+  // ---- forward: leaves -> root
+  for (int l = 0; l < nlevels; ++l) {
+    const int nov = t.ov_lvl_ptr[l + 1] - t.ov_lvl_ptr[l];
+    // (one thread per row and column of the call: the launcher sizes this grid, the only one that depends on kb)
+    if (nov > 0) add(l, overflow_sum_kernel_family, {}, 0, 256, 0, t.ov_lvl_ptr[l]).nwg = nov;
+    const int nsingle = t.h_fwd_nsingle[l], nmulti = t.h_fwd_ptr[l + 1] - t.h_fwd_ptr[l] - nsingle;
+    const bool two = t.h_lvl_two[l] != 0;    // no front of this level has more than two children
+    const bool leaf = t.h_lvl_leaf[l] != 0;  // ... has children at all
+    const int nsl = leaf ? 0 : two ? 2 : kMaxS + 1;  // carry planes compiled in
+    const int nwave = t.h_wave_ptr[l + 1] - t.h_wave_ptr[l], wave0 = t.h_wave_ptr[l];
+    int nks, wpf;
+    if (nwave > 0 && wave) {  // narrow sweep: one wave per tile of the single-tile fronts, two waves per front
+      add(l, fwd_wave_kernel_family, {KB, nsl, 2}, nwave, 128, 0, wave0);
+    } else if (nwave > 0 && thin_ok && thin_fwd_shape(t.h_thin_ns[l], leaf, two, nwave, nks, wpf)) {
+      // thin fronts: one wave per block of rows, operands straight from memory
+      add(l, fwd_thin_kernel_family, {KB, nks, nsl, wpf, tri}, nwave, 64 * wpf, 0, wave0);
+    } else if (nsingle > 0) {
+      // (the direct-fragment path of 16 columns reads all 64 rows of the block and keeps only the vector block in LDS)
+      const int kd = (kpt == 4) ? TW : t.h_fwd_kd[l];
+      add_tiles(l, fwd_level_kernel_family, {kpt, true, nsl, false, false}, lds_tiles(kd, kpt != 4), t.h_fwd_ptr[l],
+                nsingle, kd, false, false);
+    }
+    if (nmulti > 0) {
+      const int nslm = two ? 2 : kMaxS + 1;
+      // v1 of the level's fronts once, then row-tile workgroups that read it as it lies
+      const int npre = mfma ? t.h_pre_ptr[l + 1] - t.h_pre_ptr[l] : 0;
+      if (npre > 0) add(l, v1_assemble_kernel_family, {kpt, nslm}, npre, kThreads, 0, t.h_pre_ptr[l]);
+      add_tiles(l, fwd_level_kernel_family, {kpt, false, nslm, mfma, npre > 0}, mfma ? lds_frag : lds_tiles(TW, true),
+                t.h_fwd_ptr[l] + nsingle, nmulti, TW, true, mfma);
+    }
+  }
+  // ---- backward: root -> leaves
+  for (int l = nlevels - 1; l >= 0; --l) {
+    const int nsb = t.h_bwd_nsingle[l], nmulti = t.h_bwd_ptr[l + 1] - t.h_bwd_ptr[l] - nsb;
+    const int nwave = t.h_wave_ptr[l + 1] - t.h_wave_ptr[l], wave0 = t.h_wave_ptr[l];
+    if (nmulti > 0) {  // fronts with several column tiles: full 64-row tiles; 32 columns: the border's index list in LDS
+      const bool lidx = kpt >= 8 && t.h_bwd_mxbs[l] <= kLidxMax;
+      const unsigned lds = !mfma ? lds_tiles(TW, true)
+                                 : lds_frag + (lidx ? 4u * static_cast<unsigned>((t.h_bwd_mxbs[l] + 3) & ~3) : 0u);
+      add_tiles(l, bwd_level_kernel_family, {kpt, false, mfma, lidx}, lds, t.h_bwd_ptr[l] + nsb, nmulti, TW, true, mfma);
+    }
+    int nob, ch;
+    if (nwave > 0 && wave)  // narrow sweep: the single-tile fronts go wave by wave
+      add(l, bwd_wave_kernel_family, {KB}, nwave, 64, 0, wave0);
+    else if (nwave > 0 && mfma && thin_bwd_shape(t.h_thin_ns[l], t.h_thin_bs[l], nwave, nob, ch))
+      add(l, bwd_thin_kernel_family, {KB, nob, ch, tri}, nwave, 64, 0, wave0);
+    else if (nsb > 0)  // single-column-tile fronts: LDS tiles as tall as the level needs
+      add_tiles(l, bwd_level_kernel_family, {kpt, true, false, false}, lds_tiles(t.h_bwd_kd[l], true), t.h_bwd_ptr[l], nsb,
+                t.h_bwd_kd[l], false, false);
+  }
+  return out;
+}
+
+// sweep_launches(), with a kernel the table lacks reported as an internal error
+int checked_sweep_launches(const SweepTables& t, int nlevels, int kpt, bool tri, bool thin_buf,
+                           std::vector<PlannedLaunch>& out) {
+  out = sweep_launches(t, nlevels, kpt, tri, thin_buf);
+  for (const PlannedLaunch& L : out)
+    if (L.variant < 0) {
+      set_error("level %d of the %d-column sweep asks for %s<%d, %d, %d, %d, %d>, which is not in the kernel table", L.level,
+                4 * kpt, kSweepFamilyName[L.family], L.targ[0], L.targ[1], L.targ[2], L.targ[3], L.targ[4]);
+      return EIGD_E_INTERNAL;
+    }
+  return EIGD_OK;
+}
+
+// One sweep of kb <= KBMAX columns: walks the factor's list of planned launches for kb's width class
 int sweep(eigd_factor* f, const SweepCopies& cp, hipStream_t st, const SweepWorkspace& ws, const double* dIn, int ldin,
           double* dX, int ldx, int kb, double alpha, SweepRecord* rec) {
-  double *wV = ws.V, *wY = ws.Y, *wP = ws.P;
-  int* wT = ws.tickets;
-  const Symbolic& s = *f->sym;
+  double *wV = ws.V, *wY = ws.Y;
   const FrontArrays fa = f->fa();
-  // every sweep width (KB = 4, 8, 16, 32 columns) has its own set of carry planes: rows are KB wide and the
+  // every sweep width (KB = 4, 16, 32 columns) has its own set of carry planes: rows are KB wide and the
   // entries no child writes stay zero for good
-  constexpr int KB = 4 * KPT;
+  const int kpt = sweep_kpt(kb), KB = 4 * kpt;
   // (the planes of pre-assembled right-hand sides lie behind the carry planes of ALL widths: with one more plane inside
   // every width's set the thin forward kernels of the shell model ran 4 to 10 % slower -- same kernels, same bytes, other
   // addresses)
   const int ncarry = f->nplanes - (f->has_v1 ? 1 : 0);
   double* const wV1 = f->has_v1 ? wV + static_cast<int64_t>(ncarry) * f->v_rows * kPlaneCols + f->v_rows * (KB - 4) : nullptr;
   wV += static_cast<int64_t>(ncarry) * f->v_rows * (KB - 4);  // 4 + 8 + ... below KB = KB - 4
-  // multi-tile levels: every XCD gets a contiguous range of the level's records (see xcd_record)
-  auto level_args = [&](const WgRec* wg, int kd = TW, int nwg = 0, bool multi = false) {
-    LevelArgs la;
-    la.wg = wg;
-    la.P = wP;
-    la.tickets = wT;
-    la.kb = kb;
-    la.kd = kd;
-    la.nwg = nwg;
-    la.per_xcd = multi ? (nwg + 7) / 8 : 0;
-    la.V1 = wV1;
-    return la;
-  };
-  auto multi_grid = [&](int nwg) { return dim3(8 * ((nwg + 7) / 8)); };
-  auto lds_bytes = [](int kd) { return static_cast<unsigned>(sizeof(double) * (kd + 1) * (TLD + Tile<KPT>::BLD)); };
-  // fronts with several column tiles, MFMA widths: matrix operands straight from the fragment-major copies (only the
-  // vector block in LDS); the vector-FMA widths stage the column-major panels through LDS
-  const unsigned lds_frag = static_cast<unsigned>(sizeof(double) * (TW + 1) * Tile<KPT>::BLD);
-  const double* sF = cp.fF;  // the panels [T; M21] in place (F and T), forward side
-  const double* sT = cp.fT;
-  // raw buffer accesses take 32-bit byte offsets: a carry plane and the caller's block must stay below 4 GB, else the
-  // single-tile fronts of the MFMA widths go through the tile kernels
-  const bool thin_buf = f->v_rows * static_cast<int64_t>(KB) * 8 <= kBufMax && static_cast<int64_t>(s.n) * ldin * 8 <= kBufMax;
-  // ---- forward: leaves -> root.  Y receives S z, the border rows of V the carries.
-  for (int l = 0; l < s.nlevels; ++l) {
-    const int nov = f->ov_lvl_ptr[l + 1] - f->ov_lvl_ptr[l];
-    if (nov > 0) {
-      const int first = f->ov_lvl_ptr[l];
-      const int64_t plane = f->v_rows * KB;
-      if (rec) rec->launches.push_back({SweepVariant<overflow_sum_kernel_family>::id, l, kb});
-      hipLaunchKernelGGL(overflow_sum_kernel, dim3((nov * kb + 255) / 256), dim3(256), 0, st, nov, f->d_ov_dst + first,
-                         f->d_ov_ptr + first, f->d_ov_src, kb, KB, wV + (f->nslot - 1) * plane, wV + f->nslot * plane);
-      EIGD_LAUNCH_CHECK();
+  const int64_t plane = f->v_rows * KB;
+  const bool thin_buf = static_cast<int64_t>(f->sym->n) * ldin * 8 <= kBufMax;
+  for (const PlannedLaunch& L : f->launches[kpt / 4][fa.tri][thin_buf]) {
+    const SweepKernel& k = sweep_kernels()[static_cast<size_t>(L.variant)];
+    if (rec) rec->launches.push_back({L.variant, L.level, kb});
+    // (overflow_sum: one thread per surplus row and column of the call, the only grid that depends on kb)
+    const dim3 grid(L.family == overflow_sum_kernel_family ? (L.nwg * kb + 255) / 256 : L.grid), block(L.block);
+    const WgRec* tiles = (L.family == bwd_level_kernel_family ? f->d_bwd_wg : f->d_fwd_wg) + L.first;
+    const LevelArgs la{tiles, ws.P, ws.tickets, kb, L.kd, L.nwg, L.per_xcd, wV1};
+    const WgRec* waves = f->d_wave_wg + L.first;
+    switch (L.family) {
+#define EIGD_SWEEP_LAUNCH(KERNEL, ...) \
+  case KERNEL##_family: hipLaunchKernelGGL(k.as<KERNEL##_family>(), grid, block, L.lds, st, __VA_ARGS__); break
+      // the carries of the surplus children: scratch plane -> extra plane
+      EIGD_SWEEP_LAUNCH(overflow_sum_kernel, L.nwg, f->d_ov_dst + L.first, f->d_ov_ptr + L.first, f->d_ov_src, kb, KB,
+                        wV + (f->nslot - 1) * plane, wV + f->nslot * plane);
+      // forward: Y receives S z, the border rows of V the carries.  The panels [T; M21] in place (F and T) or fragment-major
+      EIGD_SWEEP_LAUNCH(fwd_wave_kernel, fa, waves, cp.fF, cp.fT, dIn, ldin, alpha, wV, wY, kb);
+      EIGD_SWEEP_LAUNCH(fwd_thin_kernel, fa, waves, dIn, ldin, alpha, wV, wY, kb, cp.Fb);
+      EIGD_SWEEP_LAUNCH(v1_assemble_kernel, fa, f->d_pre_wg + L.first, dIn, ldin, alpha, wV, wV1, kb);
+      EIGD_SWEEP_LAUNCH(fwd_level_kernel, fa, la, L.frag ? cp.Fm : cp.fF, cp.fT, dIn, ldin, alpha, wV, wY);
+      // backward: straight into the caller's block
+      EIGD_SWEEP_LAUNCH(bwd_level_kernel, fa, la, cp.bF, cp.bT, L.frag ? cp.Bm : cp.Ft, wY, dX, ldx);
+      EIGD_SWEEP_LAUNCH(bwd_wave_kernel, fa, waves, cp.Ft, wY, dX, ldx, kb);
+      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, fa, waves, cp.Ft, wY, dX, ldx, kb);
+#undef EIGD_SWEEP_LAUNCH
     }
-    const int nwg = f->h_fwd_ptr[l + 1] - f->h_fwd_ptr[l], nsingle = f->h_fwd_nsingle[l];
-    const bool two = f->h_lvl_two[l] != 0;  // no front of this level has more than two children
-    const bool leaf = f->h_lvl_leaf[l] != 0;  // ... has children at all
-    const int nwave = f->h_wave_ptr[l + 1] - f->h_wave_ptr[l];
-    bool narrow = false;
-    if (KPT <= kWaveMaxKpt) {
-      if (nwave > 0) {  // narrow sweep: one wave per tile of the single-tile fronts, two waves per front
-        const WgRec* recs = f->d_wave_wg + f->h_wave_ptr[l];
-        if (leaf)
-          EIGD_SWEEP_LAUNCH(fwd_wave_kernel, (KB, 0, 2), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin, alpha, wV,
-                             wY, kb);
-        else if (two)
-          EIGD_SWEEP_LAUNCH(fwd_wave_kernel, (KB, 2, 2), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin, alpha, wV,
-                             wY, kb);
-        else
-          EIGD_SWEEP_LAUNCH(fwd_wave_kernel, (KB, kMaxS + 1, 2), dim3(nwave), dim3(128), 0, st, fa, recs, sF, sT, dIn, ldin,
-                             alpha, wV, wY, kb);
-        EIGD_LAUNCH_CHECK();
-        narrow = true;
-      }
-    }
-    if constexpr (KPT >= 4) {
-      const int nks = f->h_thin_fwd[l];
-      if (!narrow && nwave > 0 && nks > 0 && thin_buf) {  // thin fronts: one wave per block of rows, operands straight from memory
-        const WgRec* recs = f->d_wave_wg + f->h_wave_ptr[l];
-#define EIGD_THIN_FWD(NKS, NSLV, WPFV)                                                                                   \
-  do {                                                                                                                   \
-    if (fa.tri)                                                                                                          \
-      EIGD_SWEEP_LAUNCH(fwd_thin_kernel, (KB, NKS, NSLV, WPFV, true), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
-                         alpha, wV, wY, kb, cp.Fb);                                                                    \
-    else                                                                                                                 \
-      EIGD_SWEEP_LAUNCH(fwd_thin_kernel, (KB, NKS, NSLV, WPFV, false), dim3(nwave), dim3(64 * WPFV), 0, st, fa, recs, dIn, ldin, \
-                         alpha, wV, wY, kb, cp.Fb);                                                                    \
-  } while (0)
-        if (!leaf && two && nks >= 12) {
-          // fronts of 33 to 64 own columns with carry planes: as many waves per front as give the level >= 2048 waves
-          const int wpf = (nwave >= 2048) ? 1 : (nwave >= 1024) ? 2 : 4;
-          if (nks == 12 && wpf == 1)
-            EIGD_THIN_FWD(12, 2, 1);
-          else if (nks == 12 && wpf == 2)
-            EIGD_THIN_FWD(12, 2, 2);
-          else if (nks == 12)
-            EIGD_THIN_FWD(12, 2, 4);
-          else if (wpf == 1)
-            EIGD_THIN_FWD(16, 2, 1);
-          else if (wpf == 2)
-            EIGD_THIN_FWD(16, 2, 2);
-          else
-            EIGD_THIN_FWD(16, 2, 4);
-        } else if (leaf && nks == 4)
-          EIGD_THIN_FWD(4, 0, 1);
-        else if (leaf && nks == 8)
-          EIGD_THIN_FWD(8, 0, 1);
-        else if (leaf && nks == 12)
-          EIGD_THIN_FWD(12, 0, 1);
-        else if (leaf && nks == 14)
-          EIGD_THIN_FWD(14, 0, 1);
-        else if (leaf)
-          EIGD_THIN_FWD(16, 0, 1);
-        else if (nks == 4 && two)
-          EIGD_THIN_FWD(4, 2, 1);
-        else if (nks == 4)
-          EIGD_THIN_FWD(4, kMaxS + 1, 1);
-        else if (nks == 8 && two)
-          EIGD_THIN_FWD(8, 2, 1);
-        else if (nks == 8)
-          EIGD_THIN_FWD(8, kMaxS + 1, 1);
-        else if (two)
-          EIGD_THIN_FWD(16, 2, 1);
-        else
-          EIGD_THIN_FWD(16, kMaxS + 1, 1);
-#undef EIGD_THIN_FWD
-        EIGD_LAUNCH_CHECK();
-        narrow = true;
-      }
-    }
-    if (!narrow && nsingle > 0) {
-      const int kd = (KPT == 4) ? TW : f->h_fwd_kd[l];  // (the direct-fragment path reads all 64 rows of the block)
-      const LevelArgs la = level_args(f->d_fwd_wg + f->h_fwd_ptr[l], kd);
-      auto lds_bytes = [](int kd) {  // (shadows the general one: the direct-fragment path keeps only the vector block)
-        return static_cast<unsigned>(sizeof(double) * (kd + 1) * ((KPT == 4 ? 0 : TLD) + Tile<KPT>::BLD));
-      };
-      if (leaf)
-        EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, true, 0, false, false), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st, fa, la,
-                           sF, sT, dIn, ldin, alpha, wV, wY);
-      else if (two)
-        EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, true, 2, false, false), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st, fa, la,
-                           sF, sT, dIn, ldin, alpha, wV, wY);
-      else
-        EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, true, kMaxS + 1, false, false), dim3(nsingle), dim3(kThreads), lds_bytes(kd), st,
-                           fa, la, sF, sT, dIn, ldin, alpha, wV, wY);
-      EIGD_LAUNCH_CHECK();
-    }
-    if (nwg > nsingle) {
-      const LevelArgs la = level_args(f->d_fwd_wg + f->h_fwd_ptr[l] + nsingle, TW, nwg - nsingle, true);
-      if constexpr (Tile<KPT>::kMfma) {
-        const int npre = f->h_pre_ptr[l + 1] - f->h_pre_ptr[l];
-        if (npre > 0) {  // v1 of the level's fronts once, then row-tile workgroups that read it as it lies
-          const WgRec* pre = f->d_pre_wg + f->h_pre_ptr[l];
-          if (two) {
-            EIGD_SWEEP_LAUNCH(v1_assemble_kernel, (KPT, 2), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin, alpha, wV,
-                               wV1, kb);
-            EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, true, true), multi_grid(nwg - nsingle), dim3(kThreads),
-                               lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
-          } else {
-            EIGD_SWEEP_LAUNCH(v1_assemble_kernel, (KPT, kMaxS + 1), dim3(npre), dim3(kThreads), 0, st, fa, pre, dIn, ldin,
-                               alpha, wV, wV1, kb);
-            EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, true, true), multi_grid(nwg - nsingle),
-                               dim3(kThreads), lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
-          }
-        } else if (two)
-          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, true, false), multi_grid(nwg - nsingle), dim3(kThreads),
-                             lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
-        else
-          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, true, false), multi_grid(nwg - nsingle),
-                             dim3(kThreads), lds_frag, st, fa, la, cp.Fm, sT, dIn, ldin, alpha, wV, wY);
-      } else {
-        if (two)
-          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, 2, false, false), multi_grid(nwg - nsingle), dim3(kThreads),
-                             lds_bytes(TW), st, fa, la, sF, sT, dIn, ldin, alpha, wV, wY);
-        else
-          EIGD_SWEEP_LAUNCH(fwd_level_kernel, (KPT, false, kMaxS + 1, false, false), multi_grid(nwg - nsingle), dim3(kThreads),
-                             lds_bytes(TW), st, fa, la, sF, sT, dIn, ldin, alpha, wV, wY);
-      }
-      EIGD_LAUNCH_CHECK();
-    }
-  }
-  // ---- backward: root -> leaves, straight into the caller's block.
-  for (int l = s.nlevels - 1; l >= 0; --l) {
-    const int nwg = f->h_bwd_ptr[l + 1] - f->h_bwd_ptr[l];
-    if (nwg == 0) continue;
-    const int nwave = f->h_wave_ptr[l + 1] - f->h_wave_ptr[l];
-    const int nsb = f->h_bwd_nsingle[l];
-    const bool narrow = KPT <= kWaveMaxKpt && nwave > 0;  // narrow sweep: the single-tile fronts go wave by wave
-    bool thin = false;
-    if constexpr (KPT >= 4) thin = !narrow && nwave > 0 && f->h_thin_bwd[l] > 0;
-    if (nwg > nsb) {  // fronts with several column tiles: full 64-row tiles
-      const LevelArgs la = level_args(f->d_bwd_wg + f->h_bwd_ptr[l] + nsb, TW, nwg - nsb, true);
-      if constexpr (Tile<KPT>::kMfma) {
-        if (KPT >= 8 && f->h_bwd_mxbs[l] <= kLidxMax)
-          EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, true, (KPT >= 8)), multi_grid(nwg - nsb), dim3(kThreads),
-                             lds_frag + 4u * static_cast<unsigned>((f->h_bwd_mxbs[l] + 3) & ~3), st, fa, la, cp.bF, cp.bT, cp.Bm,
-                             wY, dX, ldx);
-        else
-          EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, true, false), multi_grid(nwg - nsb), dim3(kThreads), lds_frag, st, fa,
-                             la, cp.bF, cp.bT, cp.Bm, wY, dX, ldx);
-      }
-      else
-        EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, false, false, false), multi_grid(nwg - nsb), dim3(kThreads), lds_bytes(TW), st, fa, la, cp.bF,
-                           cp.bT, cp.Ft, wY, dX, ldx);
-      EIGD_LAUNCH_CHECK();
-    }
-    if (narrow) {
-      EIGD_SWEEP_LAUNCH(bwd_wave_kernel, (KB), dim3(nwave), dim3(64), 0, st, fa, f->d_wave_wg + f->h_wave_ptr[l], cp.Ft,
-                         wY, dX, ldx, kb);
-      EIGD_LAUNCH_CHECK();
-    } else if (thin) {
-      if constexpr (KPT >= 4) {
-        const WgRec* recs = f->d_wave_wg + f->h_wave_ptr[l];
-        const int nks = f->h_thin_bwd[l];
-#define EIGD_THIN_BWD(NOB, CHV)                                                                                   \
-  do {                                                                                                            \
-    if (fa.tri)                                                                                                   \
-      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, true), dim3(nwave), dim3(64), 0, st, fa, recs, cp.Ft, wY, \
-                         dX, ldx, kb);                                                                            \
-    else                                                                                                          \
-      EIGD_SWEEP_LAUNCH(bwd_thin_kernel, (KB, NOB, CHV, false), dim3(nwave), dim3(64), 0, st, fa, recs, cp.Ft, \
-                         wY, dX, ldx, kb);                                                                        \
-  } while (0)
-        if (nks == 4)
-          EIGD_THIN_BWD(1, 8);
-        else if (nks == 8)
-          EIGD_THIN_BWD(2, 8);
-        else
-          EIGD_THIN_BWD(4, 4);
-#undef EIGD_THIN_BWD
-        EIGD_LAUNCH_CHECK();
-      }
-    } else if (nsb > 0) {  // single-column-tile fronts: LDS tiles as tall as the level needs
-      EIGD_SWEEP_LAUNCH(bwd_level_kernel, (KPT, true, false, false), dim3(nsb), dim3(kThreads), lds_bytes(f->h_bwd_kd[l]), st, fa,
-                         level_args(f->d_bwd_wg + f->h_bwd_ptr[l], f->h_bwd_kd[l]), cp.bF, cp.bT, cp.Ft, wY, dX, ldx);
-      EIGD_LAUNCH_CHECK();
-    }
+    EIGD_LAUNCH_CHECK();
   }
   return EIGD_OK;
 }
-#undef EIGD_SWEEP_LAUNCH
-#undef EIGD_UNPAREN
 
 }  // namespace
 
@@ -3352,6 +3332,15 @@ static int create_factor(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, e
   }
   // the caller's CSR data array may be longer (upper-triangle entries after the last lower one): we copy a prefix
   f->data_len = maxsrc + 1;
+  int rc = EIGD_OK;
+  for (int i = 0; i < 12 && rc == EIGD_OK; ++i) {
+    const int kpt = (i < 4) ? 1 : (i < 8) ? 4 : 8, tri = (i >> 1) & 1, thin_buf = i & 1;
+    rc = checked_sweep_launches(plan, s.nlevels, kpt, tri != 0, thin_buf != 0, f->launches[kpt / 4][tri][thin_buf]);
+  }
+  if (rc != EIGD_OK) {
+    delete f;
+    return rc;
+  }
   f->bufs = factor_buffers(f, plan);
   size_t need = size_t(64) << 20;
   for (const DeviceBuffer& b : f->bufs) need += b.bytes();
@@ -3360,7 +3349,7 @@ static int create_factor(eigd_ctx* ctx, eigd_symbolic* h, const double* hdata, e
     delete f;
     return EIGD_E_HIP;
   }
-  int rc = allocate(f->bufs, ctx->stream, f->bytes);
+  rc = allocate(f->bufs, ctx->stream, f->bytes);
   if (rc == EIGD_OK) rc = numeric(f, hdata);
   if (rc != EIGD_OK) {
     eigd_factor_free(f);
@@ -3402,14 +3391,7 @@ static int solve_blocks(eigd_factor* f, hipStream_t st, SweepWorkspace& ws, cons
   const SweepCopies cp = f->copies();
   for (int c0 = 0; c0 < k; c0 += KBMAX) {
     const int kb = std::min(KBMAX, k - c0);
-    int rc;
-    // 5 to 8 columns go through the 16-column kernels, whose single-tile levels are MFMA wave kernels (1.26 -> 1.09 ms)
-    if (kb <= 4)
-      rc = sweep<1>(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
-    else if (kb <= 16)
-      rc = sweep<4>(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
-    else
-      rc = sweep<8>(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
+    const int rc = sweep(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
     if (rc != EIGD_OK) return rc;
   }
   return EIGD_OK;
@@ -3453,9 +3435,24 @@ int eigd_factor_lane_solve_to(eigd_lane* l, const double* dIn, int ldin, double*
 
 int eigd_sweep_variants(const char** names, int cap, int* count) {
   EIGD_REQUIRE(count && (cap <= 0 || names), "null argument");
-  const std::vector<std::string>& t = sweep_variant_table();
+  const std::vector<SweepKernel>& t = sweep_kernels();
   *count = static_cast<int>(t.size());
-  for (int i = 0; i < cap && i < *count; ++i) names[i] = t[static_cast<size_t>(i)].c_str();
+  for (int i = 0; i < cap && i < *count; ++i) names[i] = t[static_cast<size_t>(i)].name.c_str();
+  return EIGD_OK;
+}
+
+int eigd_symbolic_sweep_plan(eigd_symbolic* h, int k, int tri, int thin_buf, int* variant, int* level, int cap, int* count) {
+  EIGD_REQUIRE(h && count && (cap <= 0 || (variant && level)), "null argument");
+  EIGD_REQUIRE(k >= 1 && k <= KBMAX, "a sweep has 1 to %d columns, not %d", KBMAX, k);
+  const SweepPlan plan = plan_sweeps(h->s, pre_assembly_min_workgroups());
+  std::vector<PlannedLaunch> list;
+  const int rc = checked_sweep_launches(plan, h->s.nlevels, sweep_kpt(k), tri != 0, thin_buf != 0, list);
+  if (rc != EIGD_OK) return rc;
+  *count = static_cast<int>(list.size());
+  for (int i = 0; i < cap && i < *count; ++i) {
+    variant[i] = list[static_cast<size_t>(i)].variant;
+    level[i] = list[static_cast<size_t>(i)].level;
+  }
   return EIGD_OK;
 }
 

@@ -1066,6 +1066,20 @@ class Symbolic:
             raise KeyError(name)
         return out[:ln]
 
+    def sweep_plan(self, k, tri=True, thin_buf=True):
+        """
+        the launches a ``k``-column solve of a factor on this analysis is planned to make, as (variant name, level) in
+        launch order (host only) -- ``tri`` False: after a Bunch-Kaufman numeric phase; ``thin_buf`` False: the caller's
+        block reaches beyond 4 GB.  ``Factor.sweep_record`` states what ran
+        """
+        cnt = C.c_int()
+        call("eigd_symbolic_sweep_plan", self.h, int(k), int(tri), int(thin_buf), None, None, 0, C.byref(cnt))
+        variant, level = np.empty(max(cnt.value, 1), dtype=np.int32), np.empty(max(cnt.value, 1), dtype=np.int32)
+        call("eigd_symbolic_sweep_plan", self.h, int(k), int(tri), int(thin_buf), hptr(variant), hptr(level), cnt.value,
+             C.byref(cnt))
+        names = sweep_variants()
+        return [(names[v], int(l)) for v, l in zip(variant[:cnt.value], level[:cnt.value])]
+
 
 def sweep_variants():
     """names of every kernel variant the compiled sweeps can launch, e.g. 'fwd_thin_kernel<32, 12, 2, 2, true>' (host only)"""

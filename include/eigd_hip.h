@@ -114,6 +114,13 @@ int eigd_symbolic_free(eigd_symbolic* s);
  *        [5]=sum of front dimensions [6]=max front dimension [7]=border entries [8]=lower nnz of A
  *        [9]=number of (level, step) launches [10]=flops of the numeric factorisation [11]=max columns in a front */
 int eigd_symbolic_sizes(eigd_symbolic* s, int64_t* out, int nout);
+/* the launches a k-column sweep (1 <= k <= 32) of a factor on this analysis is planned to make, host only (no device
+ * needed): *count launches in launch order, the first min(count, cap) as (index into eigd_sweep_variants, level of the
+ * assembly tree).  tri != 0: triangular diagonal blocks (Cholesky, LU), 0: after a Bunch-Kaufman numeric phase;
+ * thin_buf != 0: the caller's block ends below 4 GB (n * ld * 8 <= 0xFFFFFFF0).  Honours EIGD_PRE_MIN_WG as the
+ * creation of a factor does.  A solve records exactly these launches (eigd_factor_sweep_record). */
+int eigd_symbolic_sweep_plan(eigd_symbolic* s, int k, int tri, int thin_buf, int* variant, int* level, int cap,
+                             int* count);
 /* copy-out of the symbolic arrays (tests emulate the numeric phase in numpy from these); int64 "u_src" / "u_dst" (the
  * scatter of the strictly upper entries of an LU factor: nnz - lower nnz entries each) are built on demand */
 int eigd_symbolic_get_i32(eigd_symbolic* s, const char* name, int32_t* out, int64_t cap);
@@ -141,7 +148,8 @@ int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out);
 int eigd_factor_lane_free(eigd_lane* lane);
 int eigd_factor_lane_solve_to(eigd_lane* lane, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha);
 /* launch record of the sweeps (tests: which kernel variant ran at which level).
- * eigd_sweep_variants: every kernel variant the compiled sweeps can launch, host only (no device needed); *count
+ * eigd_sweep_variants: the kernel variants of the sweeps, host only (no device needed): the library compiles exactly
+ *   these, and the launch policy can ask for no other (a factor whose plan did would fail its creation); *count
  *   variants, names[i] for i < min(count, cap) point to static strings "family<template arguments>" spelled the way a
  *   kernel trace prints them, e.g. "fwd_thin_kernel<32, 12, 2, 2, true>".
  * eigd_factor_record_sweeps: on != 0 makes every solve of the factor and of its lanes record its launches (off, the

@@ -1,6 +1,6 @@
 """
-Catalog of the triangular sweep's launch variants (csrc/factor.hip, sweep<KPT>): which small problem makes the
-launcher pick which kernel, at which level of the assembly tree.  Plain data, no GPU import.
+Catalog of the triangular sweep's launch variants (csrc/factor.hip, sweep_launches): which small problem makes the
+launch policy pick which kernel, at which level of the assembly tree.  Plain data, no GPU import.
 
 Each Case names a matrix builder with its Symbolic parameters, the shift (None: SPD, Cholesky fronts;
 "indefinite": between two well-separated eigenvalues, Bunch-Kaufman fronts, TRI = false), the sweep widths it solves,
@@ -9,10 +9,12 @@ solves is checked to contain them).  ``replicas`` > 1: the matrix is block diago
 block scaled by powers of four (replica i = 4**scale(i) * A0); levels are heights in the assembly tree, so the same
 front of every replica lands on one level, which is how the thresholds on the number of fronts of a level are reached.
 
-EXCLUDED lists the variants the compiled sweeps contain but cannot launch, each with the reason read from the code.
-tests/test_gpu_sweep_variants.py runs the cases; test_sweep_catalog_covers_every_variant (CPU) checks that the
-targets and EXCLUDED together are exactly the library's variant table, so a change of the launch policy that adds or
-removes a variant fails until this file is updated.
+The library compiles exactly the variants its launch policy can ask for (factor.hip: sweep_kernels, sweep_launches),
+and every one of them is a target here: test_sweep_catalog_covers_every_variant (CPU) checks that the targets are
+exactly the library's variant table, so a change of the launch policy that adds or removes a variant fails until this
+file is updated.  test_planned_launches_hold_every_target (CPU) asks the policy itself, through Symbolic.sweep_plan,
+whether a case's symbolic analysis plans its targets; tests/test_gpu_sweep_variants.py runs the cases and checks that
+what ran is what was planned.
 """
 from dataclasses import dataclass, field
 
@@ -172,29 +174,6 @@ CASES += [
 BIG_CASE = Case("grid128x256_ld8192", lambda: grid_matrix(128, 256, 2), widths=(16, 32),
                 targets=_mfma(lambda KPT: ((f"fwd_level_kernel<{KPT}, true, 0, false, false>", 0),)))
 
-
-def _excluded():
-    ex = {}
-    for KB in (16, 32):
-        for nsl in (0, 2, 5):
-            ex[f"fwd_wave_kernel<{KB}, {nsl}, 2>"] = (
-                "compiled into sweep<4>/sweep<8> behind `KPT <= kWaveMaxKpt` (2): only the 4-column sweep runs it")
-        ex[f"bwd_wave_kernel<{KB}>"] = ex[f"fwd_wave_kernel<{KB}, 0, 2>"]
-        for tri in ("true", "false"):
-            for wpf in (1, 2, 4):
-                ex[f"fwd_thin_kernel<{KB}, 16, 2, {wpf}, {tri}>"] = (
-                    "16 K-steps at a level with children needs > 48 own columns, above the thin cap (48 binary, 32 else)")
-            ex[f"fwd_thin_kernel<{KB}, 16, 5, 1, {tri}>"] = (
-                "fronts with more than two children are thin only up to 32 own columns: NKS <= 8")
-    for nsl in (0, 2, 5):
-        ex[f"fwd_level_kernel<1, true, {nsl}, false, false>"] = (
-            "4-column sweeps run every single-tile front through the wave kernels")
-    ex["bwd_level_kernel<1, true, false, false>"] = "4-column sweeps run every single-tile front through bwd_wave_kernel"
-    return ex
-
-
-# variant name -> why no test can launch it
-EXCLUDED = _excluded()
 
 # conditions (not variants) no case reaches: carry planes of 4 GB or more (v_rows * KB * 8 > kBufMax) send the thin
 # levels to the tile kernels as a caller's block beyond 4 GB does (BIG_CASE); it would take a factor of ~17 M rows

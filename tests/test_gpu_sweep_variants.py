@@ -1,5 +1,5 @@
 """
-Every launch variant of the multi-RHS triangular sweep (csrc/factor.hip: sweep<KPT>, solve_blocks) against a
+Every launch variant of the multi-RHS triangular sweep (csrc/factor.hip: sweep_launches, sweep) against a
 reference: one parametrised test per case of tests/sweep_catalog.py states which kernels ran (the factor's launch
 record) and checks what they computed -- forward error per replica block and column against scipy's LU refined twice
 with residuals summed in extended precision, the row-wise backward error, and the bitwise invariants the design
@@ -189,6 +189,9 @@ def test_sweep_variants_ran_and_match_the_reference(ctx, case):
             X[w] = solve(ctx, F, B[:, :w])
     assert_targets_ran(case, rec)
     assert {kb for _, _, kb in rec} == set(case.widths)
+    with environment(case.env):                            # plan and launcher cannot drift apart
+        for w in case.widths:
+            assert [(v, l) for v, l, kb in rec if kb == w] == P.sym.sweep_plan(w, tri=case.shift is None), (case.name, w)
     kmax = max(case.widths)
     Xref = P.reference(B)
     fe = forward_errors(P, X[kmax], Xref)
@@ -288,6 +291,8 @@ def test_thin_buffer_edge(ctx):
         with F.sweep_record() as rec:
             F.solve_inplace(view)
             F.solve_inplace(big.cols(ld - 48, ld - 32).copy_from(ctx.from_host(B[:, :16])))
+        assert [(v, l) for v, l, _ in rec] == [
+            p for w in (32, 16) for p in F.symbolic.sweep_plan(w, thin_buf=n * ld * 8 <= 0xFFFFFFF0)], ld
         names = {v for v, _, _ in rec}
         thin = {v for v in names if v.startswith("fwd_thin_kernel<")}
         if n * ld * 8 <= 0xFFFFFFF0:                      # kBufMax
