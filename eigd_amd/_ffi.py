@@ -55,6 +55,9 @@ _SIGNATURES = {
     "eigd_csr_upload": [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, P(c_vp)],
     "eigd_csr_upload_rect": [c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, P(c_vp)],
     "eigd_csr_update_values": [c_vp, c_vp],
+    "eigd_csr_transpose_pattern": [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "eigd_csr_transpose": [c_vp, P(c_vp)],
+    "eigd_csr_transpose_refresh": [c_vp, c_vp],
     "eigd_mat_free": [c_vp],
     "eigd_spmm": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl],
     "eigd_spmm_on": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl],
@@ -71,9 +74,11 @@ _SIGNATURES = {
     "eigd_factor_free": [c_vp],
     "eigd_factor_solve": [c_vp, c_vp, c_int, c_int, c_dbl],
     "eigd_factor_solve_to": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl],
+    "eigd_factor_solve_transposed_to": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl],
     "eigd_factor_lane_create": [c_vp, c_vp, P(c_vp)],
     "eigd_factor_lane_free": [c_vp],
     "eigd_factor_lane_solve_to": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl],
+    "eigd_factor_lane_solve_transposed_to": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl],
     "eigd_sweep_variants": [c_vp, c_int, P(c_int)],
     "eigd_factor_record_sweeps": [c_vp, c_int],
     "eigd_factor_sweep_record": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, P(c_int)],

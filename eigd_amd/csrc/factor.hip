@@ -525,6 +525,9 @@ __global__ __launch_bounds__(kThreads) void syrk_kernel(FrontArrays fa, const in
 //   trailing update A22 -= L21 U12 over the whole square: lower part into F, upper part into FU (lu_update_kernel)
 // After the numeric phase the L side (F, inv(M_L)) and the U side (FU, inv(U)^T) each get T, M21 and the sweep copies
 // from the existing kernels: the forward sweep reads the L side, the backward sweep the U side, as it reads L^T.
+// The transposed solve (A^T = UU^T LL^T, eigd_factor_solve_transposed_to) exchanges the sides: forward over the U side,
+// backward over the L side.  Every backward kernel sums R(r, o) y(r) over the true entries of [T; M21], so the dense,
+// unsymmetric diagonal blocks inv(M_L) are applied transposed without a kernel of their own.
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -2424,6 +2427,12 @@ struct eigd_factor : SweepTables {
   // L side; an LU factor of an unsymmetric matrix (eigd_factor_create_lu) has a U side too: the sweeps read forward
   // the L side, backward the U side.  Fb and Fm are forward copies: the L side's
   FactorSide L, U;
+  // A transposed solve of an LU factor (A^T = UU^T LL^T) reads forward the U side, backward the L side (whose Ft and Bm
+  // every numeric phase builds).  The U side's forward copies exist from the first transposed solve on
+  // (ensure_transposed_copies); from then on every numeric phase fills them.
+  double *d_FbU = nullptr, *d_FmU = nullptr;
+  bool transposed_copies = false;
+  std::mutex transposed_mutex;  // lanes may meet in the first transposed solve
   // what a sweep launches (sweep_launches), per [width class][tri][thin_buf]: built once when the factor is created, so
   // that a solve walks a list and allocates nothing, and a hole in the kernel table fails the creation
   std::vector<PlannedLaunch> launches[3][2][2];
@@ -2444,6 +2453,8 @@ struct eigd_factor : SweepTables {
     const FactorSide& b = lu ? U : L;
     return SweepCopies{L.F, L.T, d_Fb, d_Fm, b.F, b.T, b.Ft, b.Bm};
   }
+  // ... and of the transposed solve of an LU factor: the sides change places
+  SweepCopies transposed_copies_of_lu() const { return SweepCopies{U.F, U.T, d_FbU, d_FmU, L.F, L.T, L.Ft, L.Bm}; }
 
   FrontArrays fa() const {
     FrontArrays a;
@@ -2605,9 +2616,13 @@ int numeric(eigd_factor* f, const double* data, bool on_device = false, bool piv
   }
   // T and M21 of every side; then the copies.  The copy kernels write the forward and the backward copies together:
   // an LU factor's U side goes first, and what it leaves in the forward copies (Fb, Fm) the L side overwrites entry
-  // for entry; the L side's backward copies land in Ft / Bm, which an LU factor's sweeps do not read
+  // for entry; the L side's backward copies land in Ft / Bm, which only the transposed sweeps of an LU factor read.
+  // Once a transposed solve has asked for them, the U side's forward copies go to buffers of their own.
   for (int i = nsides - 1; i >= 0; --i) {
     const FactorSide& sd = *sides[i];
+    const bool own_fwd = i == 1 && f->transposed_copies;
+    double* const Fb = own_fwd ? f->d_FbU : f->d_Fb;
+    double* const Fm = own_fwd ? f->d_FmU : f->d_Fm;
     if (f->n_tri > 0) {
       hipLaunchKernelGGL(trinv_kernel, dim3(f->n_tri), dim3(kThreads), 0, st, fa, f->d_tri_pref, s.nfronts, sd.F, sd.Inv,
                          sd.T);
@@ -2619,12 +2634,12 @@ int numeric(eigd_factor* f, const double* data, bool on_device = false, bool piv
     }
     if (f->n_tr > 0) {
       hipLaunchKernelGGL(transpose_front_kernel, dim3(f->n_tr), dim3(kThreads), 0, st, fa, f->d_tr_pref, s.nfronts,
-                         f->d_ftoff, sd.F, sd.T, sd.Ft, f->d_Fb);
+                         f->d_ftoff, sd.F, sd.T, sd.Ft, Fb);
       EIGD_LAUNCH_CHECK();
     }
     if (f->n_mt > 0) {
       hipLaunchKernelGGL(pack_frag_kernel, dim3(f->n_mt), dim3(kThreads), 0, st, fa, f->d_ff, f->d_mt_pref, f->n_ff, sd.F,
-                         sd.T, f->d_Fm, sd.Bm);
+                         sd.T, Fm, sd.Bm);
       EIGD_LAUNCH_CHECK();
     }
   }
@@ -3382,13 +3397,58 @@ int eigd_factor_solve(eigd_factor* f, double* dX, int ldx, int k, double alpha) 
   return eigd_factor_solve_to(f, dX, ldx, dX, ldx, k, alpha);
 }
 
+// The U side's forward copies (Fb, Fm), which only a transposed solve reads: allocated and filled from the resident
+// U.F / U.T by the first one (the copy kernels rewrite U.Ft / U.Bm with the values they hold).  They join the factor's
+// buffer table; a failed allocation leaves the factor as it was.
+static int ensure_transposed_copies(eigd_factor* f) {
+  std::lock_guard<std::mutex> guard(f->transposed_mutex);
+  if (f->transposed_copies) return EIGD_OK;
+  hipStream_t st = f->ctx->stream;
+  std::vector<DeviceBuffer> t = {device_buffer("FbU", f->d_FbU, f->ft_doubles), device_buffer("FmU", f->d_FmU, f->fm_doubles)};
+  size_t bytes = 0;
+  int rc = allocate(t, st, bytes);
+  if (rc == EIGD_OK) {
+    const FrontArrays fa = f->fa();
+    hipError_t e = hipSuccess;
+    if (f->n_tr > 0) {
+      hipLaunchKernelGGL(transpose_front_kernel, dim3(f->n_tr), dim3(kThreads), 0, st, fa, f->d_tr_pref, f->sym->nfronts,
+                         f->d_ftoff, f->U.F, f->U.T, f->U.Ft, f->d_FbU);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess && f->n_mt > 0) {
+      hipLaunchKernelGGL(pack_frag_kernel, dim3(f->n_mt), dim3(kThreads), 0, st, fa, f->d_ff, f->d_mt_pref, f->n_ff, f->U.F,
+                         f->U.T, f->d_FmU, f->U.Bm);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (a lane's stream reads them next)
+    if (e != hipSuccess) {
+      set_error("filling the transposed copies failed: %s", hipGetErrorString(e));
+      rc = EIGD_E_HIP;
+    }
+  }
+  if (rc != EIGD_OK) {
+    release(t);
+    return rc;
+  }
+  f->bufs.insert(f->bufs.end(), t.begin(), t.end());
+  f->bytes += bytes;
+  f->transposed_copies = true;
+  return EIGD_OK;
+}
+
+// trans: Out <- alpha M^-T In.  A symmetric factor's transposed solve is its solve
 static int solve_blocks(eigd_factor* f, hipStream_t st, SweepWorkspace& ws, const double* dIn, int ldin, double* dOut,
-                        int ldout, int k, double alpha) {
+                        int ldout, int k, double alpha, bool trans = false) {
   EIGD_REQUIRE(f && dIn && dOut, "null argument");
   EIGD_REQUIRE(k >= 1 && ldin >= k && ldout >= k, "bad block shape k=%d ldin=%d ldout=%d", k, ldin, ldout);
+  trans = trans && f->lu;
+  if (trans) {
+    const int rc = ensure_transposed_copies(f);
+    if (rc != EIGD_OK) return rc;
+  }
   SweepRecord* rec = f->record_sweeps ? &ws.rec : nullptr;
   if (rec) rec->launches.clear();
-  const SweepCopies cp = f->copies();
+  const SweepCopies cp = trans ? f->transposed_copies_of_lu() : f->copies();
   for (int c0 = 0; c0 < k; c0 += KBMAX) {
     const int kb = std::min(KBMAX, k - c0);
     const int rc = sweep(f, cp, st, ws, dIn + c0, ldin, dOut + c0, ldout, kb, alpha, rec);
@@ -3400,6 +3460,12 @@ static int solve_blocks(eigd_factor* f, hipStream_t st, SweepWorkspace& ws, cons
 int eigd_factor_solve_to(eigd_factor* f, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha) {
   EIGD_REQUIRE(f, "null argument");
   return solve_blocks(f, f->ctx->stream, f->ws, dIn, ldin, dOut, ldout, k, alpha);
+}
+
+int eigd_factor_solve_transposed_to(eigd_factor* f, const double* dIn, int ldin, double* dOut, int ldout, int k,
+                                    double alpha) {
+  EIGD_REQUIRE(f, "null argument");
+  return solve_blocks(f, f->ctx->stream, f->ws, dIn, ldin, dOut, ldout, k, alpha, true);
 }
 
 int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out) {
@@ -3431,6 +3497,12 @@ int eigd_factor_lane_free(eigd_lane* l) {
 int eigd_factor_lane_solve_to(eigd_lane* l, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha) {
   EIGD_REQUIRE(l, "null argument");
   return solve_blocks(l->f, l->ctx->stream, l->ws, dIn, ldin, dOut, ldout, k, alpha);
+}
+
+int eigd_factor_lane_solve_transposed_to(eigd_lane* l, const double* dIn, int ldin, double* dOut, int ldout, int k,
+                                         double alpha) {
+  EIGD_REQUIRE(l, "null argument");
+  return solve_blocks(l->f, l->ctx->stream, l->ws, dIn, ldin, dOut, ldout, k, alpha, true);
 }
 
 int eigd_sweep_variants(const char** names, int cap, int* count) {
@@ -3477,11 +3549,12 @@ int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int*
 
 int eigd_factor_stats(eigd_factor* f, double* out, int nout) {
   EIGD_REQUIRE(f && out && nout >= 1, "null argument");
-  const double v[9] = {static_cast<double>(f->sym->nnzL), static_cast<double>(f->bytes), f->sym->flops,
+  const double v[10] = {static_cast<double>(f->sym->nnzL), static_cast<double>(f->bytes), f->sym->flops,
                        static_cast<double>(f->sym->nfronts), static_cast<double>(f->n_negative),
                        static_cast<double>(f->n_perturbed), static_cast<double>(f->nplanes),
-                       f->lu ? 1.0 : 0.0, static_cast<double>(f->n_interchanges)};
-  for (int i = 0; i < nout && i < 9; ++i) out[i] = v[i];
+                       f->lu ? 1.0 : 0.0, static_cast<double>(f->n_interchanges),
+                       f->transposed_copies ? 1.0 : 0.0};
+  for (int i = 0; i < nout && i < 10; ++i) out[i] = v[i];
   return EIGD_OK;
 }
 

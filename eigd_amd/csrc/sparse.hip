@@ -38,6 +38,7 @@ struct eigd_mat {
   int32_t* tile_ptr = nullptr;    // ntiles + 1 : offsets into ucols
   int32_t* ucols = nullptr;       // distinct columns of each tile, ascending
   uint16_t* lidx = nullptr;       // per non-zero: position of its column in the tile's list
+  int32_t* tperm = nullptr;       // transposed companion (eigd_csr_transpose): data[j] = data of the original[tperm[j]]
 };
 
 namespace eigd {
@@ -397,6 +398,13 @@ __global__ __launch_bounds__(kThreads) void tile_dots_reduce_kernel(const double
   }
 }
 
+// values of the transposed companion from the original's: dst[j] = src[perm[j]] (coalesced on dst)
+__global__ __launch_bounds__(kThreads) void gather_values_kernel(int64_t nnz, const int32_t* __restrict__ perm,
+                                                                const double* __restrict__ src, double* __restrict__ dst) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+  for (int64_t j = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; j < nnz; j += stride) dst[j] = src[perm[j]];
+}
+
 }  // namespace eigd
 
 using namespace eigd;
@@ -522,6 +530,76 @@ int eigd_csr_update_values_dev(eigd_mat* A, const double* dvals) {
   return EIGD_OK;
 }
 
+// Host only: the CSR pattern of A^T (n x ncols -> ncols x n) and the permutation perm with vals(A^T)[j] = vals(A)[perm[j]].
+// A counting sort by column that keeps the order of the rows: the entries of a row of A^T come out by ascending column,
+// duplicates in A's order -- what scipy's A.T.tocsr() gives.
+int eigd_csr_transpose_pattern(int n, int ncols, const int32_t* indptr, const int32_t* indices, int32_t* t_indptr,
+                               int32_t* t_indices, int32_t* t_perm) {
+  EIGD_REQUIRE(indptr && indices && t_indptr && t_indices && t_perm, "null argument");
+  EIGD_REQUIRE(n >= 0 && ncols >= 0 && indptr[0] == 0, "bad matrix size %d x %d", n, ncols);
+  const int64_t nnz = indptr[n];
+  for (int i = 0; i < n; ++i) EIGD_REQUIRE(indptr[i + 1] >= indptr[i], "indptr not monotone at row %d", i);
+  for (int64_t e = 0; e < nnz; ++e)
+    EIGD_REQUIRE(indices[e] >= 0 && indices[e] < ncols, "column index out of range at entry %lld", (long long)e);
+  std::fill(t_indptr, t_indptr + ncols + 1, 0);
+  for (int64_t e = 0; e < nnz; ++e) ++t_indptr[indices[e] + 1];
+  for (int c = 0; c < ncols; ++c) t_indptr[c + 1] += t_indptr[c];
+  std::vector<int32_t> next(t_indptr, t_indptr + ncols);
+  for (int i = 0; i < n; ++i)
+    for (int32_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+      const int32_t j = next[indices[e]]++;
+      t_indices[j] = i;
+      t_perm[j] = e;
+    }
+  return EIGD_OK;
+}
+
+// The transposed companion of a square matrix: an ordinary eigd_mat of A^T (eigd_spmm runs on it as on any other) that
+// remembers where its values sit in A.  The pattern is read back from the device once; eigd_csr_transpose_refresh
+// brings the companion's values up to date from A's on the device.
+int eigd_csr_transpose(eigd_mat* A, eigd_mat** out) {
+  EIGD_REQUIRE(A && out, "null argument");
+  EIGD_REQUIRE(A->n == A->ncols, "the transposed companion is for square matrices, not %d x %d", A->n, A->ncols);
+  *out = nullptr;
+  const int n = A->n;
+  const size_t nnz = static_cast<size_t>(A->nnz);
+  std::vector<int32_t> ip(static_cast<size_t>(n) + 1), ix(nnz + 1), tip(static_cast<size_t>(n) + 1), tix(nnz + 1), perm(nnz + 1);
+  std::vector<double> dv(nnz + 1), tdv(nnz + 1);
+  EIGD_HIP(hipSetDevice(A->ctx->device));
+  EIGD_HIP(hipStreamSynchronize(A->ctx->stream));
+  EIGD_HIP(hipMemcpy(ip.data(), A->indptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
+  if (nnz > 0) {
+    EIGD_HIP(hipMemcpy(ix.data(), A->indices, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
+    EIGD_HIP(hipMemcpy(dv.data(), A->data, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+  }
+  int rc = eigd_csr_transpose_pattern(n, n, ip.data(), ix.data(), tip.data(), tix.data(), perm.data());
+  if (rc != EIGD_OK) return rc;
+  for (size_t j = 0; j < nnz; ++j) tdv[j] = dv[static_cast<size_t>(perm[j])];
+  eigd_mat* At = nullptr;
+  rc = eigd_csr_upload_rect(A->ctx, n, n, A->nnz, tip.data(), tix.data(), tdv.data(), &At);
+  if (rc != EIGD_OK) return rc;
+  if (hipMalloc(reinterpret_cast<void**>(&At->tperm), sizeof(int32_t) * (nnz + 1)) != hipSuccess) {
+    eigd_mat_free(At);
+    set_error("hipMalloc failed for the transposed companion (nnz=%lld)", (long long)A->nnz);
+    return EIGD_E_HIP;
+  }
+  if (nnz > 0) EIGD_HIP(hipMemcpy(At->tperm, perm.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
+  *out = At;
+  return EIGD_OK;
+}
+
+// values of the companion <- values of A, on A's stream (after eigd_csr_update_values[_dev] of A)
+int eigd_csr_transpose_refresh(eigd_mat* At, eigd_mat* A) {
+  EIGD_REQUIRE(At && A, "null argument");
+  EIGD_REQUIRE(At->tperm && At->nnz == A->nnz && At->n == A->ncols && At->ctx->device == A->ctx->device,
+               "not a transposed companion of this matrix");
+  if (A->nnz == 0) return EIGD_OK;
+  const int nb = static_cast<int>(std::min<int64_t>((A->nnz + kThreads - 1) / kThreads, 65536));
+  hipLaunchKernelGGL(gather_values_kernel, dim3(nb), dim3(kThreads), 0, A->ctx->stream, A->nnz, At->tperm, A->data, At->data);
+  EIGD_LAUNCH_CHECK();
+  return EIGD_OK;
+}
+
 int eigd_mat_free(eigd_mat* A) {
   if (!A) return EIGD_OK;
   if (A->ctx && A->ctx->stream) (void)hipStreamSynchronize(A->ctx->stream);
@@ -532,6 +610,7 @@ int eigd_mat_free(eigd_mat* A) {
   if (A->tile_ptr) (void)hipFree(A->tile_ptr);
   if (A->ucols) (void)hipFree(A->ucols);
   if (A->lidx) (void)hipFree(A->lidx);
+  if (A->tperm) (void)hipFree(A->tperm);
   delete A;
   return EIGD_OK;
 }

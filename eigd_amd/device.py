@@ -950,6 +950,16 @@ class CSRMatrix:
         h = c_vp()
         call("eigd_csr_upload_rect", ctx.h, self.n, self.ncols, self.nnz, hptr(ip), hptr(ix), hptr(dv), C.byref(h))
         self.h = h
+        self._transposed = None
+
+    @classmethod
+    def _adopt(cls, ctx, h, shape, nnz):
+        """wrap a matrix the library made (the transposed companion)"""
+        self = cls.__new__(cls)
+        self.ctx, self.h, self.shape, self.nnz = ctx, h, shape, nnz
+        self.n, self.ncols = shape
+        self._transposed = None
+        return self
 
     def __del__(self):
         try:
@@ -958,6 +968,17 @@ class CSRMatrix:
                 self.h = None
         except Exception:
             pass
+
+    def transposed(self):
+        """
+        the device matrix of A^T (square matrices): made once from the pattern, ``apply`` is bit-identical to scipy's
+        ``A.T.tocsr() @ X``; ``update_values_device`` refreshes its values on the device
+        """
+        if self._transposed is None:
+            h = c_vp()
+            call("eigd_csr_transpose", self.h, C.byref(h))
+            self._transposed = CSRMatrix._adopt(self.ctx, h, (self.ncols, self.n), self.nnz)
+        return self._transposed
 
     def apply(self, X, Y=None, alpha=1.0, beta=0.0):
         """Y = alpha A X + beta Y"""
@@ -983,6 +1004,8 @@ class CSRMatrix:
         if vals.n * vals.k < self.nnz:
             raise ValueError("value count does not match the matrix")
         call("eigd_csr_update_values_dev", self.h, vals.ptr)
+        if self._transposed is not None:
+            call("eigd_csr_transpose_refresh", self._transposed.h, self.h)
 
     def spmv_bytes(self, k=1):
         """algorithmic bytes of one product"""
@@ -1173,13 +1196,18 @@ class Factor:
         if self.stats()["static_pivots"] > 0:
             self.verify_static_pivots(CSRMatrix(self.ctx, A))
 
-    def refine(self, mat_dev, B, X, alpha=1.0, steps=1):
-        """X <- X + mat^{-1} (alpha B - mat X), ``steps`` times: iterative refinement of X ~ alpha mat^{-1} B on device blocks"""
+    def refine(self, mat_dev, B, X, alpha=1.0, steps=1, trans=False):
+        """
+        X <- X + mat^{-1} (alpha B - mat X), ``steps`` times: iterative refinement of X ~ alpha mat^{-1} B on device blocks
+        (``trans``: of X ~ alpha mat^{-T} B, residual with the transposed companion of ``mat_dev``)
+        """
         R = X.ctx.empty(X.n, X.k)
+        if trans:
+            mat_dev = mat_dev.transposed()
         for _ in range(steps):
             mat_dev.apply(X, R)
             R.assign_lincomb([(alpha, B), (-1.0, R)])
-            self.solve_to(R, R, 1.0)
+            self.solve_to(R, R, 1.0, trans=trans)
             X.assign_lincomb([(1.0, X), (1.0, R)])
         return X
 
@@ -1209,25 +1237,32 @@ class Factor:
             raise ValueError("fewer values than the analysed pattern has entries")
         call("eigd_factor_refactor_dev", self.h, vals.ptr)
 
-    def solve_inplace(self, X, alpha=1.0):
+    def solve_inplace(self, X, alpha=1.0, trans=False):
+        """X <- alpha * M^{-1} X (``trans``: alpha * M^{-T} X)"""
         if X.n != self.n:
             raise ValueError("shape mismatch in factor solve")
-        if X.ctx is not self.ctx:
-            return self.solve_to(X, X, alpha)
+        if trans or X.ctx is not self.ctx:
+            return self.solve_to(X, X, alpha, trans=trans)
         call("eigd_factor_solve", self.h, X.ptr, X.ld, X.k, float(alpha))
         self._note_sweep(None)
         return X
 
-    def solve_to(self, Xin, Xout, alpha=1.0):
-        """Xout <- alpha * M^{-1} Xin (Xin untouched); runs on the stream of Xout's context"""
+    def solve_to(self, Xin, Xout, alpha=1.0, trans=False):
+        """
+        Xout <- alpha * M^{-1} Xin (Xin untouched); runs on the stream of Xout's context.  ``trans``: alpha * M^{-T} Xin --
+        the first one of an LU factor allocates and fills the U side's forward copies (``stats()["transposed_copies"]``);
+        for a symmetric factor it is the untransposed solve
+        """
         if Xin.n != self.n or (Xout.n, Xout.k) != (Xin.n, Xin.k):
             raise ValueError("shape mismatch in factor solve")
         if Xout.ctx is self.ctx:
-            call("eigd_factor_solve_to", self.h, Xin.ptr, Xin.ld, Xout.ptr, Xout.ld, Xin.k, float(alpha))
+            call("eigd_factor_solve_transposed_to" if trans else "eigd_factor_solve_to", self.h, Xin.ptr, Xin.ld,
+                 Xout.ptr, Xout.ld, Xin.k, float(alpha))
             self._note_sweep(None)
         else:
             lane = self._lane(Xout.ctx)
-            call("eigd_factor_lane_solve_to", lane, Xin.ptr, Xin.ld, Xout.ptr, Xout.ld, Xin.k, float(alpha))
+            call("eigd_factor_lane_solve_transposed_to" if trans else "eigd_factor_lane_solve_to", lane, Xin.ptr, Xin.ld,
+                 Xout.ptr, Xout.ld, Xin.k, float(alpha))
             self._note_sweep(lane)
         return Xout
 
@@ -1275,11 +1310,12 @@ class Factor:
         return lanes[key][0]
 
     def stats(self):
-        out = np.zeros(9)
-        call("eigd_factor_stats", self.h, hptr(out), 9)
+        out = np.zeros(10)
+        call("eigd_factor_stats", self.h, hptr(out), 10)
         return {"nnzL": int(out[0]), "device_bytes": int(out[1]), "flops": float(out[2]), "nfronts": int(out[3]),
                 "negative_pivots": int(out[4]), "static_pivots": int(out[5]), "workspace_planes": int(out[6]),
-                "kind": "lu" if out[7] == 1 else "ldlt", "row_interchanges": int(out[8])}
+                "kind": "lu" if out[7] == 1 else "ldlt", "row_interchanges": int(out[8]),
+                "transposed_copies": int(out[9])}
 
     def solve_bytes(self, k):
         b = C.c_double()

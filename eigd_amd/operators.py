@@ -56,6 +56,11 @@ class SpLuOperator(LinearOperator):
     64-column panels, static pivots as above, and every application refined once against the true matrix (three
     times with static pivots).  An LU factor gives no inertia: ``negative_pivots`` is ``None``; ``kind`` is ``"lu"``
     (``"ldlt"`` for the symmetric factor).
+
+    The transposed operator comes from the same factor: ``op.T``, ``op.H``, ``op.rmatvec`` and ``op.rmatmat`` apply
+    ``mat^{-T}`` (the adjoint of a state equation with an unsymmetric matrix), refined like the forward application
+    and counted in the same ``count``.  An LU factor allocates the copies only the transposed sweep reads on its first
+    transposed application; for a symmetric operator the transposed application is the forward one.
     """
 
     def __init__(self, mat, ctx=None, symbolic=None, leaf_size=0, panel_width=0, check_symmetry=True, coords=None,
@@ -117,34 +122,36 @@ class SpLuOperator(LinearOperator):
         self.negative_pivots_bounds = (max(0, self.negative_pivots - self.static_pivots),
                                        self.negative_pivots + self.static_pivots)
 
-    def _refine(self, B, X, alpha):
+    def _refine(self, B, X, alpha, trans=False):
         """X <- X + mat^{-1} (alpha B - mat X): iterative refinement on device blocks (one step; three with static pivots)"""
         # everything on X's context: with concurrent mode groups (streams > 1) X lives on a forked context whose
         # stream and sweep lane must carry the whole refinement step
-        return self.factor.refine(self._mat_dev, B, X, alpha, steps=self._refine_steps)
+        return self.factor.refine(self._mat_dev, B, X, alpha, steps=self._refine_steps, trans=trans)
 
     # -- device path (used by the drivers) ------------------------------------
-    def solve_device(self, X, alpha=1.0, count=None):
+    def solve_device(self, X, alpha=1.0, count=None, trans=False):
         """
-        X <- alpha * mat^{-1} X in place on a device block.  ``count`` is the number of columns
-        that carry a live right-hand side (finished modes of a lock-step block are zero columns);
+        X <- alpha * mat^{-1} X in place on a device block (``trans``: alpha * mat^{-T} X).  ``count`` is the number of
+        columns that carry a live right-hand side (finished modes of a lock-step block are zero columns);
         the counter then means what the reference's does: applications per mode (ref 19-22).
         """
+        trans = bool(trans) and self.kind == "lu"  # (a symmetric matrix is its own transpose)
         with self._count_lock:
             self.count += X.k if count is None else int(count)
         if self._mat_dev is None:
-            return self.factor.solve_inplace(X, alpha)
+            return self.factor.solve_inplace(X, alpha, trans=trans)
         B = X.copy()
-        self.factor.solve_inplace(X, alpha)
-        return self._refine(B, X, alpha)
+        self.factor.solve_inplace(X, alpha, trans=trans)
+        return self._refine(B, X, alpha, trans)
 
-    def solve_device_to(self, Xin, Xout, alpha=1.0, count=None):
-        """Xout <- alpha * mat^{-1} Xin on device blocks, Xin untouched"""
+    def solve_device_to(self, Xin, Xout, alpha=1.0, count=None, trans=False):
+        """Xout <- alpha * mat^{-1} Xin on device blocks, Xin untouched (``trans``: alpha * mat^{-T} Xin)"""
+        trans = bool(trans) and self.kind == "lu"
         with self._count_lock:
             self.count += Xin.k if count is None else int(count)
-        self.factor.solve_to(Xin, Xout, alpha)
+        self.factor.solve_to(Xin, Xout, alpha, trans=trans)
         if self._mat_dev is not None:
-            self._refine(Xin, Xout, alpha)
+            self._refine(Xin, Xout, alpha, trans)
         return Xout
 
     def refactor_device(self, vals, indefinite_matrix=None):
@@ -169,32 +176,76 @@ class SpLuOperator(LinearOperator):
         self._read_inertia()
         self._mat_dev = CSRMatrix(self.ctx, csr) if self._pivoted() else None
 
-    def solve_device_dual(self, Xr, Xi, count=None):
-        """complex-step operand (Xr + i Xi) <- mat^{-1} (Xr + i Xi) in place on two device blocks (see __init__)"""
+    def solve_device_dual(self, Xr, Xi, count=None, trans=False, conjugate=False):
+        """
+        complex-step operand (Xr + i Xi) <- mat^{-1} (Xr + i Xi) in place on two device blocks (see __init__).
+        ``trans``: mat^{-T}, i.e. x + i M^{-T}(db - dM^T x) with x = M^{-T} b; with ``conjugate`` mat^{-H}: + dM^T x
+        """
         if self._imag_dev is None:
             raise TypeError("solve_device_dual needs an operator built on a complex (complex-step) matrix")
-        self.solve_device(Xr, count=count)
-        T = self._imag_dev.apply(Xr)
-        Xi.assign_lincomb([(1.0, Xi), (-1.0, T)])
-        self.solve_device(Xi, count=0)
+        self.solve_device(Xr, count=count, trans=trans)
+        T = (self._imag_dev.transposed() if trans else self._imag_dev).apply(Xr)
+        Xi.assign_lincomb([(1.0, Xi), (1.0 if conjugate else -1.0, T)])
+        self.solve_device(Xi, count=0, trans=trans)
         return Xr, Xi
 
     # -- host path (reference call surface) ------------------------------------
-    def _matvec(self, x):
+    def _apply_host(self, x, adjoint):
         x = np.asarray(x)
         if self._imag_dev is not None:
             xc = x.astype(np.complex128).reshape(self.shape[0], -1)
             Xr, Xi = self.ctx.from_host(np.ascontiguousarray(xc.real)), self.ctx.from_host(np.ascontiguousarray(xc.imag))
-            self.solve_device_dual(Xr, Xi)
+            self.solve_device_dual(Xr, Xi, trans=adjoint, conjugate=adjoint)
             out = Xr.get() + 1j * Xi.get()
             return out[:, 0] if x.ndim == 1 else out
         X = self.ctx.from_host(x.astype(np.float64).reshape(self.shape[0], -1))
-        self.solve_device(X)
+        self.solve_device(X, trans=adjoint)
         out = X.get()
         return out[:, 0] if x.ndim == 1 else out
 
+    def _matvec(self, x):
+        return self._apply_host(x, False)
+
     def _matmat(self, X):
-        return self._matvec(X)
+        return self._apply_host(X, False)
+
+    # mat^{-H} x: scipy's LinearOperator builds op.H, op.T, rmatvec and rmatmat on these (op.T conjugates around them)
+    def _rmatvec(self, x):
+        return self._apply_host(x, True)
+
+    def _rmatmat(self, X):
+        return self._apply_host(X, True)
+
+    def _adjoint(self):
+        return _AdjointSpLuOperator(self)
+
+
+class _AdjointSpLuOperator(LinearOperator):
+    """``op.H``: applies ``mat^{-H}`` with ``op``'s factor and counts in ``op.count``; ``.H`` gives ``op`` back"""
+
+    def __init__(self, op):
+        self.op = op
+        self.shape = op.shape
+        self.dtype = op.dtype
+
+    @property
+    def count(self):
+        return self.op.count
+
+    def _matvec(self, x):
+        return self.op._rmatvec(x)
+
+    def _matmat(self, X):
+        return self.op._rmatmat(X)
+
+    def _rmatvec(self, x):
+        return self.op._matvec(x)
+
+    def _rmatmat(self, X):
+        return self.op._matmat(X)
+
+    def _adjoint(self):
+        return self.op
 
 
 # ---------------------------------------------------------------------------

@@ -90,6 +90,18 @@ int eigd_csr_upload_rect(eigd_ctx* ctx, int n, int ncols, int64_t nnz, const int
 int eigd_csr_update_values(eigd_mat* A, const double* hdata);
 /* the same with the values already on the device (e.g. from eigd_assemble) */
 int eigd_csr_update_values_dev(eigd_mat* A, const double* dvals);
+/* A^T X on the device.  eigd_csr_transpose_pattern (host only): the CSR pattern of A^T and the permutation t_perm with
+ * vals(A^T)[j] = vals(A)[t_perm[j]]; the entries of a row of A^T come by ascending column, duplicates in A's order
+ * (scipy's A.T.tocsr()).  t_indptr: ncols + 1 entries, t_indices and t_perm: nnz.
+ * eigd_csr_transpose: the transposed companion of a square matrix, an ordinary eigd_mat of A^T (row blocks and tile
+ * lists of its own, so eigd_spmm runs the existing kernels on it: bit-identical to scipy's A.T.tocsr() @ X) that keeps
+ * t_perm on the device.  eigd_csr_transpose_refresh: the companion's values from A's, gathered on the device on A's
+ * stream -- call it after eigd_csr_update_values[_dev] of A.  The companion is freed with eigd_mat_free, before A or
+ * after. */
+int eigd_csr_transpose_pattern(int n, int ncols, const int32_t* indptr, const int32_t* indices, int32_t* t_indptr,
+                               int32_t* t_indices, int32_t* t_perm);
+int eigd_csr_transpose(eigd_mat* A, eigd_mat** At);
+int eigd_csr_transpose_refresh(eigd_mat* At, eigd_mat* A);
 int eigd_mat_free(eigd_mat* A);
 int eigd_spmm(eigd_mat* A, const double* dX, int ldx, double* dY, int ldy, int k, double alpha, double beta);
 /* same product enqueued on another context of the same device */
@@ -143,10 +155,21 @@ int eigd_factor_free(eigd_factor* f);
 int eigd_factor_solve(eigd_factor* f, double* dX, int ldx, int k, double alpha);
 /* out of place: Out <- alpha * M^{-1} In (In is not modified; In == Out is allowed) -- Z[:, kp] = factor(W[:, kp]) (1248) */
 int eigd_factor_solve_to(eigd_factor* f, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha);
+/* transposed solve: Out <- alpha * M^{-T} In, same shapes and rules (any k >= 1, In == Out allowed).  An LU factor
+ * A = LL UU sweeps forward over its U side and backward over its L side (A^T = UU^T LL^T) with the kernels and the
+ * launch list of the untransposed solve; the sweep record works as for it.  The U side's forward copies, which no other
+ * solve reads, are allocated and filled by the first transposed solve (stats [9]; counted in the device bytes from then
+ * on, refilled by every later numeric phase); if that allocation fails the call returns EIGD_E_HIP with the size in the
+ * message and the factor stays usable for untransposed solves.  For a symmetric factor this is eigd_factor_solve_to:
+ * same launches, bitwise the same result, no memory of its own. */
+int eigd_factor_solve_transposed_to(eigd_factor* f, const double* dIn, int ldin, double* dOut, int ldout, int k,
+                                    double alpha);
 /* concurrent sweeps on one factor: a lane owns its own vector workspaces and runs on `ctx`'s stream */
 int eigd_factor_lane_create(eigd_factor* f, eigd_ctx* ctx, eigd_lane** out);
 int eigd_factor_lane_free(eigd_lane* lane);
 int eigd_factor_lane_solve_to(eigd_lane* lane, const double* dIn, int ldin, double* dOut, int ldout, int k, double alpha);
+int eigd_factor_lane_solve_transposed_to(eigd_lane* lane, const double* dIn, int ldin, double* dOut, int ldout, int k,
+                                         double alpha);
 /* launch record of the sweeps (tests: which kernel variant ran at which level).
  * eigd_sweep_variants: the kernel variants of the sweeps, host only (no device needed): the library compiles exactly
  *   these, and the launch policy can ask for no other (a factor whose plan did would fail its creation); *count
@@ -165,7 +188,8 @@ int eigd_factor_sweep_record(eigd_factor* f, eigd_lane* lane, int* variant, int*
           [5]=static pivots [6]=planes of the sweeps' vector workspace (carry planes, + 1 where the right-hand sides of
           levels with thousands of workgroups are pre-assembled)
           [7]=kind of factor (0 = L S L^T of a symmetric matrix, 1 = LU) [8]=row interchanges of the LU panels; an LU
-          factor reports 0 negative pivots (it gives no inertia) */
+          factor reports 0 negative pivots (it gives no inertia)
+          [9]=the forward copies of an LU factor's U side are held (0/1: from the first transposed solve on) */
 int eigd_factor_stats(eigd_factor* f, double* out, int nout);
 /* bytes of L streamed by one k-column solve (algorithmic, for the roofline) */
 int eigd_factor_solve_bytes(eigd_factor* f, int k, double* bytes);
