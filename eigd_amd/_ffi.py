@@ -61,6 +61,12 @@ _SIGNATURES = {
     "eigd_mat_free": [c_vp],
     "eigd_spmm": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl],
     "eigd_spmm_on": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl],
+    "eigd_ccsr_upload": [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, P(c_vp)],
+    "eigd_ccsr_update_values_dev": [c_vp, c_vp],
+    "eigd_ccsr_conjugate_transpose": [c_vp, P(c_vp)],
+    "eigd_ccsr_conjugate_transpose_refresh": [c_vp, c_vp],
+    "eigd_ccsr_spmm_on": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl],
+    "eigd_expand_values": [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp],
     "eigd_symbolic_create": [c_int, c_vp, c_vp, c_int, c_int, P(c_vp)],
     "eigd_symbolic_create_geom": [c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, P(c_vp)],
     "eigd_symbolic_free": [c_vp],

@@ -39,6 +39,9 @@ struct eigd_mat {
   int32_t* ucols = nullptr;       // distinct columns of each tile, ascending
   uint16_t* lidx = nullptr;       // per non-zero: position of its column in the tile's list
   int32_t* tperm = nullptr;       // transposed companion (eigd_csr_transpose): data[j] = data of the original[tperm[j]]
+  // complex matrix (eigd_ccsr_upload): 2 nnz doubles, real and imaginary part of every entry next to each other; `data`
+  // stays empty.  Its conjugate-transposed companion keeps an expansion table of 2 nnz entries in tperm
+  double* cdata = nullptr;
 };
 
 namespace eigd {
@@ -405,6 +408,220 @@ __global__ __launch_bounds__(kThreads) void gather_values_kernel(int64_t nnz, co
   for (int64_t j = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; j < nnz; j += stride) dst[j] = src[perm[j]];
 }
 
+
+// ---- complex matrices on split-layout blocks ------------------------------------------------------------------------
+// A complex n x k block lives as n rows of 2k doubles: columns [0, k) the real part, [k, 2k) the imaginary part -- the
+// same memory as the 2n x k block of the real-equivalent system with interleaved unknowns.  A has one index list and
+// interleaved values (16 bytes per non-zero).  Per (row, column) the sums run in CSR order with separate real and
+// imaginary accumulators; a product is (ar xr) - (ai xi) and (ar xi) + (ai xr), every operation rounded on its own:
+// bit-identical to a host loop in that order (and to scipy's complex csr_matvecs).
+// algorithmic bytes: 20 nnz + 4 n + 32 n k.
+typedef double cdbl2 __attribute__((ext_vector_type(2)));
+
+struct CAcc {
+  double re = 0.0, im = 0.0;
+  __device__ __forceinline__ void add(double ar, double ai, double xr, double xi) {
+    const double p0 = __dmul_rn(ar, xr), p1 = __dmul_rn(ai, xi);
+    const double p2 = __dmul_rn(ar, xi), p3 = __dmul_rn(ai, xr);
+    const double pr = __dsub_rn(p0, p1);
+    const double pi = __dadd_rn(p2, p3);
+    re = __dadd_rn(re, pr);
+    im = __dadd_rn(im, pi);
+  }
+};
+
+// k == 1: the row blocks of the real SpMV (at most kNnzTile - 2 non-zeros, or one long row).  The 256 lanes stream the
+// values (one 16-byte load per non-zero) and indices coalesced and stage the complex products in LDS; one lane per row
+// adds its segment in CSR order.  A long row goes through the same staging chunk by chunk, its sum kept by lane 0.
+__global__ __launch_bounds__(kThreads) void cspmv_stream_kernel(const int32_t* __restrict__ rowblocks, int nblocks,
+                                                               int nblocks_padded, const int32_t* __restrict__ indptr,
+                                                               const int32_t* __restrict__ indices,
+                                                               const cdbl2* __restrict__ vals,
+                                                               const double* __restrict__ X, int ldx, int imx,
+                                                               double* __restrict__ Y, int ldy, int imy, double alpha,
+                                                               double beta) {
+  __shared__ double pr[kNnzTile];
+  __shared__ double pi[kNnzTile];
+  const int b = xcd_remap(blockIdx.x, nblocks_padded);
+  if (b >= nblocks) return;
+  const int tid = threadIdx.x;
+  const int r0 = rowblocks[b], r1 = rowblocks[b + 1];
+  const int e0 = indptr[r0], e1 = indptr[r1];
+  auto stage = [&](int ea, int ez) {  // products of the non-zeros [ea, ez), ez - ea <= kNnzTile
+    constexpr int IT = kNnzTile / kThreads;
+    cdbl2 v[IT];
+    int col[IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+      const int e = ea + tid + it * kThreads;
+      const bool ok = e < ez;
+      v[it] = ok ? __builtin_nontemporal_load(vals + e) : cdbl2{0.0, 0.0};
+      col[it] = ok ? __builtin_nontemporal_load(indices + e) : 0;
+    }
+    double xr[IT], xi[IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+      const bool ok = ea + tid + it * kThreads < ez;
+      const double* xp = X + static_cast<int64_t>(col[it]) * ldx;
+      xr[it] = ok ? xp[0] : 0.0;
+      xi[it] = ok ? xp[imx] : 0.0;
+    }
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+      const int q = tid + it * kThreads;
+      if (ea + q < ez) {
+        const double p0 = __dmul_rn(v[it][0], xr[it]), p1 = __dmul_rn(v[it][1], xi[it]);
+        const double p2 = __dmul_rn(v[it][0], xi[it]), p3 = __dmul_rn(v[it][1], xr[it]);
+        pr[q] = __dsub_rn(p0, p1);
+        pi[q] = __dadd_rn(p2, p3);
+      }
+    }
+  };
+  auto store = [&](int r, double sr, double si) {
+    double* yp = Y + static_cast<int64_t>(r) * ldy;
+    yp[0] = (beta == 0.0) ? alpha * sr : alpha * sr + beta * yp[0];
+    yp[imy] = (beta == 0.0) ? alpha * si : alpha * si + beta * yp[imy];
+  };
+  if (e1 - e0 <= kNnzTile) {
+    stage(e0, e1);
+    __syncthreads();
+    for (int r = r0 + tid; r < r1; r += kThreads) {
+      const int a = indptr[r] - e0, z = indptr[r + 1] - e0;
+      double sr = 0.0, si = 0.0;
+      for (int q = a; q < z; ++q) {
+        sr = __dadd_rn(sr, pr[q]);
+        si = __dadd_rn(si, pi[q]);
+      }
+      store(r, sr, si);
+    }
+  } else {  // (a row block with more non-zeros than the tile is a single row)
+    double sr = 0.0, si = 0.0;
+    for (int ea = e0; ea < e1; ea += kNnzTile) {
+      const int ez = min(e1, ea + kNnzTile);
+      stage(ea, ez);
+      __syncthreads();
+      if (tid == 0)
+        for (int q = 0; q < ez - ea; ++q) {
+          sr = __dadd_rn(sr, pr[q]);
+          si = __dadd_rn(si, pi[q]);
+        }
+      __syncthreads();
+    }
+    if (tid == 0) store(r0, sr, si);
+  }
+}
+
+// k >= 1 columns (kb <= KP, KP a power of two up to 32), tiles of kTileRows rows as in spmm_tiled_kernel: the distinct
+// rows of X the tile touches are staged in LDS once, both halves of a row as contiguous pieces of kb doubles (a staged
+// row: KP real parts, KP imaginary parts, one double of padding).  Lane (row, column) then walks its row in CSR order;
+// the value of a non-zero is one 16-byte load that the lanes of the row share.  STAGED = false: the column lists do not
+// fit the LDS budget, the rows of X are gathered from global memory.
+template <bool STAGED>
+__global__ __launch_bounds__(kThreads) void cspmm_tiled_kernel(int n, int kb, int kp_log2, int ntiles, int tiles_per_xcd,
+                                                              const int32_t* __restrict__ tile_ptr,
+                                                              const int32_t* __restrict__ ucols,
+                                                              const int32_t* __restrict__ indptr,
+                                                              const int32_t* __restrict__ indices,
+                                                              const uint16_t* __restrict__ lidx,
+                                                              const cdbl2* __restrict__ vals,
+                                                              const double* __restrict__ X, int ldx, int imx,
+                                                              double* __restrict__ Y, int ldy, int imy, double alpha,
+                                                              double beta) {
+  extern __shared__ __align__(16) double Xs[];
+  const int tile = (blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);
+  if (tile >= ntiles) return;
+  const int kp = 1 << kp_log2;
+  const int c = threadIdx.x & (kp - 1), rr = threadIdx.x >> kp_log2;
+  const int rpp = kThreads >> kp_log2;  // rows per pass
+  const int ld = 2 * kp + 1;
+  const int rbeg = tile * kTileRows, rend = min(n, rbeg + kTileRows);
+  if constexpr (STAGED) {
+    const int u0 = tile_ptr[tile], nu = tile_ptr[tile + 1] - u0;
+    constexpr int SU = 8;  // staged rows per lane and trip: their loads are in flight together
+    for (int j0 = 0; j0 < nu; j0 += SU * rpp) {
+      int col[SU];
+      double xr[SU], xi[SU];
+#pragma unroll
+      for (int q = 0; q < SU; ++q) {
+        const int j = j0 + q * rpp + rr;
+        col[q] = (j < nu) ? ucols[u0 + j] : -1;
+      }
+#pragma unroll
+      for (int q = 0; q < SU; ++q) {
+        const bool ok = col[q] >= 0 && c < kb;
+        const double* xp = X + static_cast<int64_t>(ok ? col[q] : 0) * ldx + (ok ? c : 0);
+        xr[q] = ok ? xp[0] : 0.0;
+        xi[q] = ok ? xp[imx] : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < SU; ++q) {
+        const int j = j0 + q * rpp + rr;
+        if (j < nu) {
+          Xs[j * ld + c] = xr[q];
+          Xs[j * ld + kp + c] = xi[q];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (c >= kb) return;
+  for (int r = rbeg + rr; r < rend; r += rpp) {
+    const int a = indptr[r], z = indptr[r + 1];
+    CAcc s;
+    int e = a;
+    for (; e + 4 <= z; e += 4) {  // four non-zeros per trip: their loads are issued before the first add
+      cdbl2 v[4];
+      double xr[4], xi[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        v[q] = vals[e + q];
+        if constexpr (STAGED) {
+          const double* xp = Xs + static_cast<int>(lidx[e + q]) * ld + c;
+          xr[q] = xp[0];
+          xi[q] = xp[kp];
+        } else {
+          const double* xp = X + static_cast<int64_t>(indices[e + q]) * ldx + c;
+          xr[q] = xp[0];
+          xi[q] = xp[imx];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s.add(v[q][0], v[q][1], xr[q], xi[q]);
+    }
+    for (; e < z; ++e) {
+      const cdbl2 v = vals[e];
+      if constexpr (STAGED) {
+        const double* xp = Xs + static_cast<int>(lidx[e]) * ld + c;
+        s.add(v[0], v[1], xp[0], xp[kp]);
+      } else {
+        const double* xp = X + static_cast<int64_t>(indices[e]) * ldx + c;
+        s.add(v[0], v[1], xp[0], xp[imx]);
+      }
+    }
+    double* yp = Y + static_cast<int64_t>(r) * ldy + c;
+    yp[0] = (beta == 0.0) ? alpha * s.re : alpha * s.re + beta * yp[0];
+    yp[imy] = (beta == 0.0) ? alpha * s.im : alpha * s.im + beta * yp[imy];
+  }
+}
+
+// Value expansion: dst[q] = +-src[2 entry + part] with table[q] = entry << 2 | part << 1 | negate, or 0.0 where
+// table[q] < 0 (an entry the target pattern has and the source has not).  src: complex values, real and imaginary part
+// next to each other.  Serves the values of both real-equivalent forms of a complex matrix (4 nnz doubles) and the
+// values of the conjugate-transposed companion (2 nnz doubles); coalesced on dst and on the table.
+__global__ __launch_bounds__(kThreads) void expand_values_kernel(int64_t nout, const int32_t* __restrict__ table,
+                                                                const double* __restrict__ src, double* __restrict__ dst) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < nout; q += stride) {
+    const int32_t t = table[q];
+    double v = 0.0;
+    if (t >= 0) {
+      v = src[2 * static_cast<int64_t>(t >> 2) + ((t >> 1) & 1)];
+      if (t & 1) v = -v;
+    }
+    dst[q] = v;
+  }
+}
+
 }  // namespace eigd
 
 using namespace eigd;
@@ -518,6 +735,7 @@ int eigd_csr_upload_rect(eigd_ctx* ctx, int n, int ncols, int64_t nnz, const int
 
 int eigd_csr_update_values(eigd_mat* A, const double* hdata) {
   EIGD_REQUIRE(A && hdata, "null argument");
+  EIGD_REQUIRE(!A->cdata, "a complex matrix: its values are updated on the device (eigd_ccsr_update_values_dev)");
   EIGD_HIP(hipStreamSynchronize(A->ctx->stream));
   if (A->nnz > 0) EIGD_HIP(hipMemcpy(A->data, hdata, sizeof(double) * A->nnz, hipMemcpyHostToDevice));
   return EIGD_OK;
@@ -525,6 +743,7 @@ int eigd_csr_update_values(eigd_mat* A, const double* hdata) {
 
 int eigd_csr_update_values_dev(eigd_mat* A, const double* dvals) {
   EIGD_REQUIRE(A && dvals, "null argument");
+  EIGD_REQUIRE(!A->cdata, "a complex matrix: use eigd_ccsr_update_values_dev");
   if (A->nnz > 0)
     EIGD_HIP(hipMemcpyAsync(A->data, dvals, sizeof(double) * A->nnz, hipMemcpyDeviceToDevice, A->ctx->stream));
   return EIGD_OK;
@@ -560,6 +779,7 @@ int eigd_csr_transpose_pattern(int n, int ncols, const int32_t* indptr, const in
 int eigd_csr_transpose(eigd_mat* A, eigd_mat** out) {
   EIGD_REQUIRE(A && out, "null argument");
   EIGD_REQUIRE(A->n == A->ncols, "the transposed companion is for square matrices, not %d x %d", A->n, A->ncols);
+  EIGD_REQUIRE(!A->cdata, "a complex matrix: use eigd_ccsr_conjugate_transpose");
   *out = nullptr;
   const int n = A->n;
   const size_t nnz = static_cast<size_t>(A->nnz);
@@ -611,6 +831,7 @@ int eigd_mat_free(eigd_mat* A) {
   if (A->ucols) (void)hipFree(A->ucols);
   if (A->lidx) (void)hipFree(A->lidx);
   if (A->tperm) (void)hipFree(A->tperm);
+  if (A->cdata) (void)hipFree(A->cdata);
   delete A;
   return EIGD_OK;
 }
@@ -626,6 +847,7 @@ int eigd_spmm_on(eigd_ctx* ctx, eigd_mat* A, const double* dX, int ldx, double* 
   EIGD_REQUIRE(ctx->device == A->ctx->device, "context and matrix live on different devices");
   EIGD_REQUIRE(k >= 1 && ldx >= k && ldy >= k, "bad block shape k=%d ldx=%d ldy=%d", k, ldx, ldy);
   EIGD_REQUIRE(dX != dY, "spmm cannot run in place");
+  EIGD_REQUIRE(!A->cdata, "a complex matrix: use eigd_ccsr_spmm_on");
   hipStream_t st = ctx->stream;
   if (k == 1 && ldx == 1 && ldy == 1) {
     const int nbp = (A->nblocks + 7) & ~7;
@@ -704,6 +926,7 @@ int eigd_spmm_cg(eigd_ctx* ctx, eigd_mat* A, int k, const double* dZ, int ldz, d
   EIGD_REQUIRE(ctx->device == A->ctx->device, "context and matrix live on different devices");
   EIGD_REQUIRE(k >= 1 && k <= kMaxK && ldz >= k && ldy >= k && ldr >= k && A->n == A->ncols, "bad block shape k=%d", k);
   EIGD_REQUIRE(dZ != dY, "spmm cannot run in place");
+  EIGD_REQUIRE(!A->cdata, "a complex matrix has no conjugate-gradient product");
   const int kp = std::max(2, next_pow2(k));
   const int cpl = (kp >= 8) ? kp / 8 : 1;
   const size_t tile_lds = sizeof(double) * static_cast<size_t>(A->umax) * (cpl >= 2 ? kp + 4 : kp + 1);
@@ -741,6 +964,149 @@ int eigd_spmm_cg(eigd_ctx* ctx, eigd_mat* A, int k, const double* dZ, int ldz, d
   hipLaunchKernelGGL(tile_dots_reduce_kernel, dim3(groups), dim3(kThreads), 0, st, dots, A->ntiles, 2 * k, gsum);
   EIGD_LAUNCH_CHECK();
   return cg_coefficients_from_partials(ctx, gsum, groups, k, dNorm2, dState, step, first, dLog);
+}
+
+// ---- complex CSR matrices ------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kCTileLds = 64 * 1024;  // LDS of the staged X rows of the complex product (bytes)
+
+int launch_expand(hipStream_t st, int64_t nout, const int32_t* table, const double* src, double* dst) {
+  if (nout == 0) return EIGD_OK;
+  const int nb = static_cast<int>(std::min<int64_t>((nout + kThreads - 1) / kThreads, 65536));
+  hipLaunchKernelGGL(expand_values_kernel, dim3(nb), dim3(kThreads), 0, st, nout, table, src, dst);
+  EIGD_LAUNCH_CHECK();
+  return EIGD_OK;
+}
+}  // namespace
+
+int eigd_ccsr_upload(eigd_ctx* ctx, int n, int64_t nnz, const int32_t* hindptr, const int32_t* hindices,
+                     const double* hdata, eigd_mat** out) {
+  EIGD_REQUIRE(ctx && hindptr && hindices && hdata && out, "null argument");
+  EIGD_REQUIRE(nnz >= 0 && nnz < (int64_t(1) << 29), "bad complex matrix size nnz=%lld", (long long)nnz);
+  // pattern, row blocks and tile lists: those of a real matrix with the same entries
+  std::vector<double> re(static_cast<size_t>(nnz) + 1);
+  for (int64_t e = 0; e < nnz; ++e) re[e] = hdata[2 * e];
+  eigd_mat* A = nullptr;
+  int rc = eigd_csr_upload_rect(ctx, n, n, nnz, hindptr, hindices, re.data(), &A);
+  if (rc != EIGD_OK) return rc;
+  (void)hipFree(A->data);
+  A->data = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&A->cdata), sizeof(double) * (2 * nnz + 4)) != hipSuccess) {
+    eigd_mat_free(A);
+    set_error("hipMalloc failed for complex CSR values (nnz=%lld)", (long long)nnz);
+    return EIGD_E_HIP;
+  }
+  if (nnz > 0) EIGD_HIP(hipMemcpy(A->cdata, hdata, sizeof(double) * 2 * nnz, hipMemcpyHostToDevice));
+  *out = A;
+  return EIGD_OK;
+}
+
+int eigd_ccsr_update_values_dev(eigd_mat* A, const double* dvals) {
+  EIGD_REQUIRE(A && dvals, "null argument");
+  EIGD_REQUIRE(A->cdata, "not a complex matrix");
+  if (A->nnz > 0)
+    EIGD_HIP(hipMemcpyAsync(A->cdata, dvals, sizeof(double) * 2 * A->nnz, hipMemcpyDeviceToDevice, A->ctx->stream));
+  return EIGD_OK;
+}
+
+// The conjugate-transposed companion, modelled on eigd_csr_transpose: pattern and permutation once on the host; the
+// companion keeps the expansion table (entry, part, sign) of its 2 nnz doubles in tperm.
+int eigd_ccsr_conjugate_transpose(eigd_mat* A, eigd_mat** out) {
+  EIGD_REQUIRE(A && out, "null argument");
+  EIGD_REQUIRE(A->cdata && A->n == A->ncols, "not a (square) complex matrix");
+  *out = nullptr;
+  const int n = A->n;
+  const size_t nnz = static_cast<size_t>(A->nnz);
+  std::vector<int32_t> ip(static_cast<size_t>(n) + 1), ix(nnz + 1), tip(static_cast<size_t>(n) + 1), tix(nnz + 1), perm(nnz + 1);
+  std::vector<double> dv(2 * nnz + 2), tdv(2 * nnz + 2);
+  EIGD_HIP(hipSetDevice(A->ctx->device));
+  EIGD_HIP(hipStreamSynchronize(A->ctx->stream));
+  EIGD_HIP(hipMemcpy(ip.data(), A->indptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
+  if (nnz > 0) {
+    EIGD_HIP(hipMemcpy(ix.data(), A->indices, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
+    EIGD_HIP(hipMemcpy(dv.data(), A->cdata, sizeof(double) * 2 * nnz, hipMemcpyDeviceToHost));
+  }
+  int rc = eigd_csr_transpose_pattern(n, n, ip.data(), ix.data(), tip.data(), tix.data(), perm.data());
+  if (rc != EIGD_OK) return rc;
+  std::vector<int32_t> table(2 * nnz + 2);
+  for (size_t j = 0; j < nnz; ++j) {
+    const size_t p = static_cast<size_t>(perm[j]);
+    tdv[2 * j] = dv[2 * p];
+    tdv[2 * j + 1] = -dv[2 * p + 1];
+    table[2 * j] = static_cast<int32_t>(p << 2);
+    table[2 * j + 1] = static_cast<int32_t>((p << 2) | 3);
+  }
+  eigd_mat* At = nullptr;
+  rc = eigd_ccsr_upload(A->ctx, n, A->nnz, tip.data(), tix.data(), tdv.data(), &At);
+  if (rc != EIGD_OK) return rc;
+  if (hipMalloc(reinterpret_cast<void**>(&At->tperm), sizeof(int32_t) * (2 * nnz + 2)) != hipSuccess) {
+    eigd_mat_free(At);
+    set_error("hipMalloc failed for the conjugate-transposed companion (nnz=%lld)", (long long)A->nnz);
+    return EIGD_E_HIP;
+  }
+  if (nnz > 0) EIGD_HIP(hipMemcpy(At->tperm, table.data(), sizeof(int32_t) * 2 * nnz, hipMemcpyHostToDevice));
+  *out = At;
+  return EIGD_OK;
+}
+
+int eigd_ccsr_conjugate_transpose_refresh(eigd_mat* At, eigd_mat* A) {
+  EIGD_REQUIRE(At && A, "null argument");
+  EIGD_REQUIRE(At->tperm && At->cdata && A->cdata && At->nnz == A->nnz && At->n == A->ncols &&
+                   At->ctx->device == A->ctx->device,
+               "not a conjugate-transposed companion of this matrix");
+  return launch_expand(A->ctx->stream, 2 * A->nnz, At->tperm, A->cdata, At->cdata);
+}
+
+int eigd_expand_values(eigd_ctx* ctx, int64_t nout, int64_t nsrc, const int32_t* dtable, const double* dsrc,
+                       double* ddst) {
+  EIGD_REQUIRE(ctx && dtable && dsrc && ddst, "null argument");
+  EIGD_REQUIRE(nout >= 0 && nsrc >= 0 && nsrc < (int64_t(1) << 29), "bad sizes nout=%lld nsrc=%lld", (long long)nout,
+               (long long)nsrc);
+  EIGD_REQUIRE(dsrc != ddst, "the expansion cannot run in place");
+  return launch_expand(ctx->stream, nout, dtable, dsrc, ddst);
+}
+
+int eigd_ccsr_spmm_on(eigd_ctx* ctx, eigd_mat* A, const double* dX, int ldx, double* dY, int ldy, int k, double alpha,
+                      double beta) {
+  EIGD_REQUIRE(ctx && A && dX && dY, "null argument");
+  EIGD_REQUIRE(A->cdata, "not a complex matrix");
+  EIGD_REQUIRE(ctx->device == A->ctx->device, "context and matrix live on different devices");
+  EIGD_REQUIRE(k >= 1 && ldx >= 2 * k && ldy >= 2 * k, "bad block shape k=%d ldx=%d ldy=%d", k, ldx, ldy);
+  EIGD_REQUIRE(dX != dY, "spmm cannot run in place");
+  hipStream_t st = ctx->stream;
+  const cdbl2* vals = reinterpret_cast<const cdbl2*>(A->cdata);
+  if (k == 1) {
+    const int nbp = (A->nblocks + 7) & ~7;
+    hipLaunchKernelGGL(cspmv_stream_kernel, dim3(nbp), dim3(kThreads), 0, st, A->rowblocks, A->nblocks, nbp, A->indptr,
+                       A->indices, vals, dX, ldx, 1, dY, ldy, 1, alpha, beta);
+    EIGD_LAUNCH_CHECK();
+    return EIGD_OK;
+  }
+  // widest chunk of columns (a power of two up to 32) whose staged rows of X fit the LDS budget
+  auto lds_of = [&](int kp) { return sizeof(double) * static_cast<size_t>(A->umax) * (2 * kp + 1); };
+  int chunk = 32;
+  while (chunk > 1 && (A->ntiles == 0 || lds_of(chunk) > kCTileLds)) chunk >>= 1;
+  const bool staged = A->ntiles > 0 && lds_of(chunk) <= kCTileLds;
+  if (!staged) chunk = 32;
+  const int ntiles = (A->n + kTileRows - 1) / kTileRows;
+  const int per_xcd = (ntiles + 7) / 8;
+  const dim3 tgrid(per_xcd * 8);
+  for (int c0 = 0; c0 < k; c0 += chunk) {
+    const int kb = std::min(chunk, k - c0);
+    const int kp = next_pow2(kb);
+    int lg = 0;
+    while ((1 << lg) < kp) ++lg;
+    if (staged)
+      hipLaunchKernelGGL(cspmm_tiled_kernel<true>, tgrid, dim3(kThreads), lds_of(kp), st, A->n, kb, lg, ntiles, per_xcd,
+                         A->tile_ptr, A->ucols, A->indptr, A->indices, A->lidx, vals, dX + c0, ldx, k, dY + c0, ldy, k,
+                         alpha, beta);
+    else
+      hipLaunchKernelGGL(cspmm_tiled_kernel<false>, tgrid, dim3(kThreads), 0, st, A->n, kb, lg, ntiles, per_xcd,
+                         A->tile_ptr, A->ucols, A->indptr, A->indices, A->lidx, vals, dX + c0, ldx, k, dY + c0, ldy, k,
+                         alpha, beta);
+    EIGD_LAUNCH_CHECK();
+  }
+  return EIGD_OK;
 }
 
 }  // extern "C"

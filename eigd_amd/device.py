@@ -1014,6 +1014,191 @@ class CSRMatrix:
         return 12.0 * self.nnz + 4.0 * self.n + 16.0 * self.n * k
 
 
+# ---------------------------------------------------------------------------
+# complex matrices: split-layout blocks and the real-equivalent forms
+# ---------------------------------------------------------------------------
+# A complex n x k block lives on the device as n rows of 2k doubles, real part in columns [0, k), imaginary part in
+# [k, 2k).  Row-major, that is the memory of the 2n x k block with interleaved unknowns (re_0, im_0, re_1, ...): the
+# right-hand side of the real-equivalent system.  No kernel converts between the two; they are views of one block.
+
+def complex_split(x):
+    """host array (n,) or (n, k), real or complex -> float64 (n, 2k): [real part | imaginary part]"""
+    x = np.asarray(x)
+    xc = x.reshape(x.shape[0], -1)
+    out = np.empty((xc.shape[0], 2 * xc.shape[1]))
+    out[:, : xc.shape[1]] = xc.real
+    out[:, xc.shape[1]:] = xc.imag if np.iscomplexobj(xc) else 0.0
+    return out
+
+
+def complex_join(Z):
+    """float64 (n, 2k) [real part | imaginary part] -> complex128 (n, k)"""
+    k = Z.shape[1] // 2
+    return Z[:, :k] + 1j * Z[:, k:]
+
+
+def interleaved_view(Z):
+    """the 2n x k block (interleaved unknowns) that is the memory of the contiguous split-layout block Z (n x 2k)"""
+    if Z.k % 2 or Z.ld != Z.k:
+        raise ValueError("a contiguous block of an even number of columns expected")
+    return DeviceBlock(Z.ctx, 2 * Z.n, Z.k // 2, Z.buf, Z.offset, Z.k // 2)
+
+
+REAL_EQUIVALENT_FORMS = ("lu", "symmetric")
+
+
+def real_equivalent_pattern(indptr, indices, form="lu", source=None):
+    """
+    Pattern of the real-equivalent matrix of order 2n (interleaved unknowns) of a complex CSR pattern, and the table
+    that makes its values from the complex ones.  Every complex entry a + ib becomes a 2 x 2 block at its place:
+    ``form="lu"``: [[a, -b], [b, a]] (the matrix of [Ar -Ai; Ai Ar]); ``form="symmetric"``: [[a, -b], [-b, -a]]
+    (the second block row negated: symmetric where the complex matrix is).  ``source[e]``: which complex value entry e
+    of the pattern takes (default e; -1: none, the entry is an explicit zero).  Returns (indptr2, indices2, table),
+    ``table[q] = entry << 2 | part << 1 | negate`` or -1 (see expand_values_host / ValueExpansion).
+    """
+    if form not in REAL_EQUIVALENT_FORMS:
+        raise ValueError(f"form must be one of {REAL_EQUIVALENT_FORMS}")
+    ip = np.asarray(indptr, dtype=np.int64)
+    ix = np.asarray(indices, dtype=np.int64)
+    n, nnz = len(ip) - 1, len(ix)
+    if nnz >= 1 << 29:
+        raise ValueError("too many entries for the expansion table")
+    ln = np.diff(ip)
+    rows = np.repeat(np.arange(n), ln)
+    e = np.arange(nnz)
+    src = e if source is None else np.asarray(source, dtype=np.int64)
+    top = 2 * ip[rows] + 2 * e          # first entry of the block's upper row; the lower row follows 2 len(row) later
+    bot = top + 2 * ln[rows]
+    ip2 = np.empty(2 * n + 1, dtype=np.int32)
+    ip2[0:2 * n:2] = 4 * ip[:-1]
+    ip2[1:2 * n:2] = 4 * ip[:-1] + 2 * ln
+    ip2[2 * n] = 4 * nnz
+    ix2 = np.empty(4 * nnz, dtype=np.int32)
+    table = np.empty(4 * nnz, dtype=np.int32)
+    re, im, neg = src << 2, (src << 2) | 2, 1
+    lower = (im, re) if form == "lu" else (im | neg, re | neg)
+    for pos, col, code in ((top, 2 * ix, re), (top + 1, 2 * ix + 1, im | neg),
+                           (bot, 2 * ix, lower[0]), (bot + 1, 2 * ix + 1, lower[1])):
+        ix2[pos] = col
+        table[pos] = np.where(src >= 0, code, -1)
+    return ip2, ix2, table
+
+
+def expand_values_host(table, cdata):
+    """host restatement of ValueExpansion: the real values a table makes from complex ones"""
+    flat = np.ascontiguousarray(cdata, dtype=np.complex128).view(np.float64)
+    t = np.asarray(table, dtype=np.int64)
+    ok = t >= 0
+    tt = np.where(ok, t, 0)
+    v = flat[2 * (tt >> 2) + ((tt >> 1) & 1)] if flat.size else np.zeros(len(t))
+    v = np.where(tt & 1, -v, v)
+    return np.where(ok, v, 0.0)
+
+
+def real_equivalent(A, form="lu"):
+    """the real-equivalent CSR matrix (order 2n, interleaved unknowns) of a complex sparse matrix"""
+    from scipy import sparse
+
+    A = sparse.csr_matrix(A).astype(np.complex128)
+    A.sort_indices()
+    ip2, ix2, table = real_equivalent_pattern(A.indptr, A.indices, form)
+    n = A.shape[0]
+    return sparse.csr_matrix((expand_values_host(table, A.data), ix2, ip2), shape=(2 * n, 2 * n))
+
+
+class ValueExpansion:
+    """an expansion table on the device: ``expand(vals)`` makes the real values from ``nsrc`` complex ones (an nsrc x 2
+    device block: real and imaginary part per entry) without a host round trip"""
+
+    def __init__(self, ctx, table, nsrc):
+        table = np.ascontiguousarray(table, dtype=np.int32)
+        self.ctx, self.nout, self.nsrc = ctx, len(table), int(nsrc)
+        if self.nsrc >= 1 << 29 or (len(table) and int(table.max()) >> 2 >= max(self.nsrc, 1)):
+            raise ValueError("the table points past the source values")
+        self._table = _Buffer(ctx, max(table.nbytes, 8))
+        call("eigd_h2d", ctx.h, c_vp(self._table.ptr), hptr(table), table.nbytes)
+
+    def expand(self, vals, out=None):
+        if vals.n * vals.k < 2 * self.nsrc or vals.ld != vals.k:
+            raise ValueError("a contiguous block of one (real, imaginary) pair per entry expected")
+        out = out if out is not None else vals.ctx.empty(max(self.nout, 1), 1)
+        if out.n * out.k < self.nout or out.ld != out.k:
+            raise ValueError("the result block is too small")
+        call("eigd_expand_values", vals.ctx.h, self.nout, self.nsrc, c_vp(self._table.ptr), vals.ptr, out.ptr)
+        return out
+
+
+class ComplexCSRMatrix:
+    """
+    device copy of a square complex scipy CSR matrix (interleaved complex values, one index list), applied to
+    split-layout blocks: ``apply`` is bit-identical to scipy's complex ``A @ X``
+    """
+
+    dtype = np.dtype(np.complex128)
+
+    def __init__(self, ctx, A):
+        from scipy import sparse
+
+        A = sparse.csr_matrix(A).astype(np.complex128)
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("expected a square matrix")
+        self.ctx = ctx
+        self.shape = A.shape
+        self.n = self.ncols = A.shape[0]
+        self.nnz = int(A.nnz)
+        ip = np.ascontiguousarray(A.indptr, dtype=np.int32)
+        ix = np.ascontiguousarray(A.indices, dtype=np.int32)
+        dv = np.ascontiguousarray(A.data, dtype=np.complex128)
+        h = c_vp()
+        call("eigd_ccsr_upload", ctx.h, self.n, self.nnz, hptr(ip), hptr(ix), hptr(dv), C.byref(h))
+        self.h = h
+        self._conjugate_transposed = None
+
+    __del__ = CSRMatrix.__del__
+
+    def conjugate_transposed(self):
+        """the device matrix of A^H: made once from the pattern; ``update_values_device`` refreshes its values on the device"""
+        if self._conjugate_transposed is None:
+            h = c_vp()
+            call("eigd_ccsr_conjugate_transpose", self.h, C.byref(h))
+            At = ComplexCSRMatrix.__new__(ComplexCSRMatrix)
+            At.ctx, At.h, At.shape, At.nnz, At.n, At.ncols = self.ctx, h, self.shape, self.nnz, self.n, self.n
+            At._conjugate_transposed = None
+            self._conjugate_transposed = At
+        return self._conjugate_transposed
+
+    def apply(self, X2, Y2=None, alpha=1.0, beta=0.0):
+        """Y = alpha A X + beta Y on split-layout blocks (n x 2k: real half, imaginary half); alpha, beta real"""
+        if X2.k % 2:
+            raise ValueError("a split-layout block has an even number of columns")
+        if Y2 is None:
+            Y2 = X2.ctx.empty(self.n, X2.k)
+        if X2.n != self.n or (Y2.n, Y2.k) != (self.n, X2.k):
+            raise ValueError("shape mismatch in SpMM")
+        call("eigd_ccsr_spmm_on", X2.ctx.h, self.h, X2.ptr, X2.ld, Y2.ptr, Y2.ld, X2.k // 2, float(alpha), float(beta))
+        return Y2
+
+    def matvec(self, x):
+        """numpy in, numpy out (complex128)"""
+        x = np.asarray(x)
+        out = complex_join(self.apply(self.ctx.from_host(complex_split(x))).get())
+        return out[:, 0] if x.ndim == 1 else out
+
+    matmat = matvec
+
+    def update_values_device(self, vals):
+        """new values (device block nnz x 2: real and imaginary part per entry, in this matrix's CSR order), same sparsity"""
+        if vals.n * vals.k < 2 * self.nnz or vals.ld != vals.k:
+            raise ValueError("value count does not match the matrix")
+        call("eigd_ccsr_update_values_dev", self.h, vals.ptr)
+        if self._conjugate_transposed is not None:
+            call("eigd_ccsr_conjugate_transpose_refresh", self._conjugate_transposed.h, self.h)
+
+    def spmm_bytes(self, k=1):
+        """algorithmic bytes of one product with k complex columns"""
+        return 20.0 * self.nnz + 4.0 * self.n + 32.0 * self.n * k
+
+
 _I32 = ("perm", "iperm", "f_c0", "f_ns", "f_bs", "f_parent", "f_level", "f_slot", "f_npanels", "border", "rel",
         "lvl_ptr", "lvl_fronts", "lvl_nsteps", "v_src")
 _I64 = ("f_bptr", "f_foff", "f_voff", "f_ioff", "a_src", "a_dst", "u_src", "u_dst")

@@ -9,7 +9,43 @@ import numpy as np
 from scipy import sparse
 from scipy.sparse.linalg import LinearOperator
 
-from .device import CSRMatrix, Factor, default_context
+from . import tuning
+from .device import (ComplexCSRMatrix, CSRMatrix, DeviceBlock, Factor, ValueExpansion, complex_join, complex_split,
+                     default_context, expand_values_host, interleaved_view, real_equivalent_pattern, symmetrised_pattern)
+
+COMPLEX_ARITHMETIC = ("auto", "dual", "full")
+
+
+def select_complex_arithmetic(data, requested="auto"):
+    """
+    the path a complex matrix with the values ``data`` takes: "dual" (a complex-step matrix: the real factor applied to a
+    dual number) or "full" (true complex arithmetic).  "auto": "dual" where max|Im| <= tuning.complex_step_ratio max|Re|
+    """
+    if requested not in COMPLEX_ARITHMETIC:
+        raise ValueError(f"complex_arithmetic must be one of {COMPLEX_ARITHMETIC}")
+    if requested != "auto":
+        return requested
+    data = np.asarray(data)
+    if data.size == 0:
+        return "dual"
+    return "dual" if np.max(np.abs(data.imag)) <= tuning.complex_step_ratio * np.max(np.abs(data.real)) else "full"
+
+
+class _RealEquivalentOfComplex:
+    """the real-equivalent matrix of a device complex matrix, applied to 2n x k blocks (Factor.verify_static_pivots)"""
+
+    def __init__(self, cmat, form):
+        self.cmat, self.form = cmat, form
+
+    def apply(self, X, Y=None):
+        if Y is None:
+            Y = X.ctx.empty(X.n, X.k)
+        Y2 = DeviceBlock(Y.ctx, Y.n // 2, 2 * Y.k, Y.buf, Y.offset, 2 * Y.k)
+        self.cmat.apply(DeviceBlock(X.ctx, X.n // 2, 2 * X.k, X.buf, X.offset, 2 * X.k), Y2)
+        if self.form == "symmetric":  # (its second block row is the negated one)
+            im = Y2.cols(Y.k, 2 * Y.k)
+            im.assign_lincomb([(-1.0, im)])
+        return Y
 
 
 def _with_structural_diagonal(csr):
@@ -61,10 +97,24 @@ class SpLuOperator(LinearOperator):
     ``mat^{-T}`` (the adjoint of a state equation with an unsymmetric matrix), refined like the forward application
     and counted in the same ``count``.  An LU factor allocates the copies only the transposed sweep reads on its first
     transposed application; for a symmetric operator the transposed application is the forward one.
+
+    Complex matrices take one of two paths (``complex_arithmetic``; the one taken is ``op.complex_arithmetic``, ``None``
+    for a real matrix).  ``"dual"``: ``mat = M + i dM`` is a complex-step matrix, a dual number: ``M`` alone is factored
+    and ``mat^{-1}(b + i db) = x + i M^{-1}(db - dM x)``, exact to first order in ``dM``.  ``"full"``: true complex
+    arithmetic through the real-equivalent system of order 2n with interleaved unknowns, every entry ``a + ib`` a
+    block ``[[a, -b], [b, a]]``, factored by the LU path (``symmetric=False``), or for a complex *symmetric* matrix
+    (``mat == mat^T``, e.g. a damped dynamic stiffness; ``symmetric=True``) ``[[a, -b], [-b, -a]]`` factored by the
+    Bunch-Kaufman path with half the factor bytes -- its inertia is always (n, n), so ``negative_pivots`` is ``None``.
+    Every application is refined against the complex matrix itself.  ``"auto"`` (the default) takes ``"dual"`` where
+    ``max|Im| <= tuning.complex_step_ratio max|Re|`` (1e-12; complex-step perturbations are of relative size 1e-20)
+    and ``"full"`` otherwise.  In ``"full"`` mode ``op.H`` applies ``mat^{-H}`` and ``op.T`` ``mat^{-T}``;
+    ``solve_device_dual`` is the complex solve on device blocks and ``solve_device`` / ``solve_device_to`` raise.
     """
 
     def __init__(self, mat, ctx=None, symbolic=None, leaf_size=0, panel_width=0, check_symmetry=True, coords=None,
-                 symmetric=True):
+                 symmetric=True, complex_arithmetic="auto"):
+        if complex_arithmetic not in COMPLEX_ARITHMETIC:
+            raise ValueError(f"complex_arithmetic must be one of {COMPLEX_ARITHMETIC}")
         if not sparse.issparse(mat):
             mat = sparse.csr_matrix(mat)
         if mat.shape[0] != mat.shape[1]:
@@ -78,15 +128,22 @@ class SpLuOperator(LinearOperator):
         # dual number -- products of two imaginary parts vanish below rounding -- so mat^{-1}(b + i db) =
         # x + i M^{-1}(db - dM x) with x = M^{-1} b: the real factor, applied twice.
         self._imag_dev = None
+        self._cmat_dev = None            # "full": the complex matrix itself (the refinement's residuals)
+        self.complex_arithmetic = None
+        self._complex_request = complex_arithmetic
+        self.symmetric = bool(symmetric)
         if np.issubdtype(mat.dtype, np.complexfloating):
             cm = mat.tocsr()
             cm.sort_indices()
             self.dtype = np.dtype(np.complex128)
+            self.complex_arithmetic = select_complex_arithmetic(cm.data, complex_arithmetic)
+            if self.complex_arithmetic == "full":
+                self._init_full(cm, symbolic, leaf_size, panel_width, check_symmetry, coords)
+                return
             self._imag_dev = CSRMatrix(self.ctx, sparse.csr_matrix((cm.data.imag.copy(), cm.indices, cm.indptr), shape=cm.shape))
             mat = sparse.csr_matrix((cm.data.real.copy(), cm.indices, cm.indptr), shape=cm.shape)
         csr = mat.tocsr().astype(np.float64)  # for a symmetric matrix CSC and CSR coincide
         csr.sort_indices()
-        self.symmetric = bool(symmetric)
         if self.symmetric:  # (the LU factor symmetrises the pattern itself; the refinement applies csr as it is)
             csr = _with_structural_diagonal(csr)
         if check_symmetry and self.symmetric:
@@ -103,9 +160,121 @@ class SpLuOperator(LinearOperator):
         # pivots were needed)
         self._mat_dev = CSRMatrix(self.ctx, csr) if self._pivoted() else None
 
+    # -- full complex arithmetic: the real-equivalent factor -----------------------------------------------------------
+    def _real_equivalent_of(self, cm):
+        """(real-equivalent CSR matrix of the canonical complex CSR matrix ``cm``, expansion table): on the pattern the
+        factor is analysed on -- symmetrised for the LU form, with every diagonal entry for the symmetric form"""
+        n = cm.shape[0]
+        # where the entries of cm sit in that pattern: the pattern helpers carry the entry numbers along as values
+        numbered = sparse.csr_matrix((np.arange(1.0, cm.nnz + 1.0), cm.indices, cm.indptr), shape=cm.shape)
+        padded = _with_structural_diagonal(numbered) if self.symmetric else symmetrised_pattern(numbered)
+        source = padded.data.astype(np.int64) - 1
+        ip2, ix2, table = real_equivalent_pattern(padded.indptr, padded.indices, "symmetric" if self.symmetric else "lu",
+                                                  source)
+        return sparse.csr_matrix((expand_values_host(table, cm.data), ix2, ip2), shape=(2 * n, 2 * n)), table
+
+    @staticmethod
+    def _canonical_complex(mat):
+        cm = sparse.csr_matrix(mat).astype(np.complex128)
+        if not cm.has_canonical_format:
+            cm = cm.copy()
+            cm.sum_duplicates()
+        return cm
+
+    def _init_full(self, cm, symbolic, leaf_size, panel_width, check_symmetry, coords):
+        cm = self._canonical_complex(cm)
+        if check_symmetry and self.symmetric:
+            x = np.random.default_rng(0).uniform(-1.0, 1.0, size=cm.shape[0])
+            for part in (cm.real.tocsr(), cm.imag.tocsr()):
+                d = part @ x - part.T @ x
+                if np.linalg.norm(d) > 1e-10 * max(np.linalg.norm(cm @ x), 1e-300):
+                    raise ValueError("SpLuOperator (MI355X) needs a symmetric matrix; pass symmetric=False for an LU factor")
+        req, self._table = self._real_equivalent_of(cm)
+        self._pattern = (cm.indptr.copy(), cm.indices.copy())
+        self._expansion = None
+        if coords is not None:  # both unknowns of a dof sit at its node
+            coords = np.repeat(np.asarray(coords, dtype=np.float64).reshape(cm.shape[0], -1), 2, axis=0)
+        self.factor = Factor(self.ctx, req, symbolic=symbolic, leaf_size=leaf_size, panel_width=panel_width,
+                             coords=coords, lu=not self.symmetric)
+        self.symbolic = self.factor.symbolic
+        self._read_inertia()
+        self._mat_dev = None
+        self._cmat_dev = ComplexCSRMatrix(self.ctx, cm)
+
+    def _raw_full(self, Z, herm):
+        """Z <- mat^{-1} Z (``herm``: mat^{-H} Z) with the factor alone, in place on a contiguous split-layout block"""
+        k = Z.k // 2
+        im = Z.cols(k, 2 * k)
+        V = interleaved_view(Z)
+        if self.kind == "lu":  # (the transposed real-equivalent matrix is the real-equivalent of mat^H)
+            return self.factor.solve_to(V, V, 1.0, trans=herm)
+        # symmetric form [[Ar, -Ai], [-Ai, -Ar]] (xr, xi) = (br, -bi); mat^{-H} = conj o mat^{-1} o conj for mat = mat^T: the
+        # conjugation of the right-hand side and the sign of the form cancel, the solution is conjugated instead
+        if not herm:
+            im.assign_lincomb([(-1.0, im)])
+        self.factor.solve_to(V, V, 1.0)
+        if herm:
+            im.assign_lincomb([(-1.0, im)])
+        return Z
+
+    def _solve_full(self, Z, trans=False, conjugate=False):
+        """
+        Z <- mat^{-1} Z in place on a contiguous split-layout block (n x 2k), refined against the complex matrix;
+        ``trans``: mat^{-T}, with ``conjugate`` as well: mat^{-H}; ``conjugate`` alone: conj(mat)^{-1}
+        """
+        if self.kind == "lu":
+            herm, wrap = bool(trans), bool(trans) != bool(conjugate)   # mat^{-T} = conj o mat^{-H} o conj
+        else:
+            herm, wrap = bool(conjugate), False                         # mat = mat^T
+        k = Z.k // 2
+        im = Z.cols(k, 2 * k)
+        if wrap:
+            im.assign_lincomb([(-1.0, im)])
+        B = Z.copy()
+        self._raw_full(Z, herm)
+        M = self._cmat_dev.conjugate_transposed() if herm else self._cmat_dev
+        R = Z.ctx.empty(Z.n, Z.k)
+        for _ in range(self._refine_steps):
+            M.apply(Z, R)
+            R.assign_lincomb([(1.0, B), (-1.0, R)])
+            self._raw_full(R, herm)
+            Z.assign_lincomb([(1.0, Z), (1.0, R)])
+        if wrap:
+            im.assign_lincomb([(-1.0, im)])
+        return Z
+
+    def _refactor_full(self, mat):
+        if not np.issubdtype(mat.dtype, np.complexfloating):
+            raise ValueError("this operator works in full complex arithmetic: refactor it with a complex matrix")
+        cm = self._canonical_complex(mat)
+        if not (np.array_equal(cm.indptr, self._pattern[0]) and np.array_equal(cm.indices, self._pattern[1])):
+            raise ValueError("the complex matrix has a different sparsity pattern")
+        req, _ = self._real_equivalent_of(cm)
+        self.factor.refactor(req)
+        self._read_inertia()
+        self._cmat_dev = ComplexCSRMatrix(self.ctx, cm)
+
+    def expand_values_device(self, vals):
+        """("full") the real-equivalent CSR values the factor takes, from complex values on the device (nnz x 2 block)"""
+        if self._expansion is None:
+            self._expansion = ValueExpansion(self.ctx, self._table, len(self._pattern[1]))
+        return self._expansion.expand(vals)
+
+    def _refactor_device_full(self, vals, indefinite_matrix):
+        if indefinite_matrix is not None and not isinstance(indefinite_matrix, ComplexCSRMatrix):
+            raise TypeError("full complex arithmetic: the refinement needs a ComplexCSRMatrix")
+        self.factor.refactor_device(self.expand_values_device(vals))
+        self._read_inertia()
+        if indefinite_matrix is not None:
+            self._cmat_dev = indefinite_matrix
+        else:                        # (every application is refined: the operator's own matrix takes the new values)
+            self._cmat_dev.update_values_device(vals)
+        if self.static_pivots > 0:
+            self.factor.verify_static_pivots(_RealEquivalentOfComplex(self._cmat_dev, "lu" if self.kind == "lu" else "symmetric"))
+
     def _pivoted(self):
-        # (an LU factor pivots inside its panels only: always refined)
-        return self.kind == "lu" or self.negative_pivots > 0 or self.static_pivots > 0
+        # (an LU factor pivots inside its panels only: always refined; so is every full-complex application)
+        return self.complex_arithmetic == "full" or self.kind == "lu" or self.negative_pivots > 0 or self.static_pivots > 0
 
     def _read_inertia(self):
         st = self.factor.stats()
@@ -113,7 +282,7 @@ class SpLuOperator(LinearOperator):
         self.row_interchanges = st["row_interchanges"]
         self.static_pivots = st["static_pivots"]   # pivots singular inside their panel block, replaced by +-sqrt(eps)|A|
         self._refine_steps = self.factor.STATIC_PIVOT_REFINEMENTS if self.static_pivots > 0 else 1
-        if self.kind == "lu":  # no inertia
+        if self.kind == "lu" or self.complex_arithmetic == "full":  # no inertia (the symmetric real-equivalent form: always (n, n))
             self.negative_pivots = self.negative_pivots_bounds = None
             return
         self.negative_pivots = st["negative_pivots"]
@@ -135,6 +304,7 @@ class SpLuOperator(LinearOperator):
         columns that carry a live right-hand side (finished modes of a lock-step block are zero columns);
         the counter then means what the reference's does: applications per mode (ref 19-22).
         """
+        self._no_real_block("solve_device")
         trans = bool(trans) and self.kind == "lu"  # (a symmetric matrix is its own transpose)
         with self._count_lock:
             self.count += X.k if count is None else int(count)
@@ -144,8 +314,13 @@ class SpLuOperator(LinearOperator):
         self.factor.solve_inplace(X, alpha, trans=trans)
         return self._refine(B, X, alpha, trans)
 
+    def _no_real_block(self, name):
+        if self.complex_arithmetic == "full":
+            raise TypeError(f"{name}: a real block has no imaginary half; a full-complex operator takes solve_device_dual")
+
     def solve_device_to(self, Xin, Xout, alpha=1.0, count=None, trans=False):
         """Xout <- alpha * mat^{-1} Xin on device blocks, Xin untouched (``trans``: alpha * mat^{-T} Xin)"""
+        self._no_real_block("solve_device_to")
         trans = bool(trans) and self.kind == "lu"
         with self._count_lock:
             self.count += Xin.k if count is None else int(count)
@@ -158,8 +333,12 @@ class SpLuOperator(LinearOperator):
         """
         numeric refactorisation from CSR values on the device (``ElementAssembler.assemble``; the pattern must be the
         one this operator was built on).  The positive definite case needs nothing else; for an indefinite result pass
-        the device CSRMatrix holding the same values (``indefinite_matrix``) for the refinement step.
+        the device CSRMatrix holding the same values (``indefinite_matrix``) for the refinement step.  Full complex
+        arithmetic: ``vals`` is an nnz x 2 block (real and imaginary part per entry, CSR order of the matrix the operator
+        was built on), ``indefinite_matrix`` a ComplexCSRMatrix holding them (None: the operator's own takes them).
         """
+        if self.complex_arithmetic == "full":
+            return self._refactor_device_full(vals, indefinite_matrix)
         self.factor.refactor_device(vals)
         self._read_inertia()
         if self._pivoted() and indefinite_matrix is None:
@@ -169,7 +348,13 @@ class SpLuOperator(LinearOperator):
             self.factor.verify_static_pivots(self._mat_dev)
 
     def refactor(self, mat):
-        """numeric refactorisation with new values on the same sparsity pattern"""
+        """numeric refactorisation with new values on the same sparsity pattern (a complex matrix stays on the path --
+        ``complex_arithmetic`` -- the operator was built on: switching between "dual" and "full" raises)"""
+        if self.complex_arithmetic == "full":
+            return self._refactor_full(mat)
+        if np.issubdtype(mat.dtype, np.complexfloating) and select_complex_arithmetic(
+                mat.tocsr().data, "dual" if self._complex_request == "dual" else "auto") == "full":
+            raise ValueError("this operator was not built for full complex arithmetic: make a new one for this matrix")
         csr = mat.tocsr().astype(np.float64)
         csr.sort_indices()
         self.factor.refactor(csr)
@@ -179,8 +364,28 @@ class SpLuOperator(LinearOperator):
     def solve_device_dual(self, Xr, Xi, count=None, trans=False, conjugate=False):
         """
         complex-step operand (Xr + i Xi) <- mat^{-1} (Xr + i Xi) in place on two device blocks (see __init__).
-        ``trans``: mat^{-T}, i.e. x + i M^{-T}(db - dM^T x) with x = M^{-T} b; with ``conjugate`` mat^{-H}: + dM^T x
+        ``trans``: mat^{-T}, i.e. x + i M^{-T}(db - dM^T x) with x = M^{-T} b; with ``conjugate`` mat^{-H}: + dM^T x.
+        Full complex arithmetic: the true complex solve; in place without a copy when Xr and Xi are the two halves of
+        one contiguous n x 2k block (``Z.cols(0, k)``, ``Z.cols(k, 2 k)``), else through such a block
         """
+        if self.complex_arithmetic == "full":
+            k = Xr.k
+            if (Xi.n, Xi.k) != (Xr.n, k) or Xr.n != self.shape[0]:
+                raise ValueError("shape mismatch in the complex solve")
+            with self._count_lock:
+                self.count += k if count is None else int(count)
+            halves = Xr.buf is Xi.buf and Xr.ld == Xi.ld == 2 * k and Xi.offset == Xr.offset + k
+            if halves:
+                Z = DeviceBlock(Xr.ctx, Xr.n, 2 * k, Xr.buf, Xr.offset, 2 * k)
+            else:
+                Z = Xr.ctx.empty(Xr.n, 2 * k)
+                Z.cols(0, k).copy_from(Xr)
+                Z.cols(k, 2 * k).copy_from(Xi)
+            self._solve_full(Z, trans=trans, conjugate=conjugate)
+            if not halves:
+                Xr.copy_from(Z.cols(0, k))
+                Xi.copy_from(Z.cols(k, 2 * k))
+            return Xr, Xi
         if self._imag_dev is None:
             raise TypeError("solve_device_dual needs an operator built on a complex (complex-step) matrix")
         self.solve_device(Xr, count=count, trans=trans)
@@ -192,6 +397,12 @@ class SpLuOperator(LinearOperator):
     # -- host path (reference call surface) ------------------------------------
     def _apply_host(self, x, adjoint):
         x = np.asarray(x)
+        if self.complex_arithmetic == "full":
+            Z = self.ctx.from_host(complex_split(x.reshape(self.shape[0], -1)))
+            k = Z.k // 2
+            self.solve_device_dual(Z.cols(0, k), Z.cols(k, 2 * k), trans=adjoint, conjugate=adjoint)
+            out = complex_join(Z.get())
+            return out[:, 0] if x.ndim == 1 else out
         if self._imag_dev is not None:
             xc = x.astype(np.complex128).reshape(self.shape[0], -1)
             Xr, Xi = self.ctx.from_host(np.ascontiguousarray(xc.real)), self.ctx.from_host(np.ascontiguousarray(xc.imag))

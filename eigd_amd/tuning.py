@@ -35,6 +35,11 @@ host_twins = "returned"    # "returned": the device block a returned psi was dow
                            # a content sample of 1024 rows + first and last page only (an edit between sampled rows goes
                            # unnoticed: opt-in).  False: every call transfers what it is given, results are writable
 
+# ---- complex matrices (operators.py: SpLuOperator(complex_arithmetic="auto"))
+complex_step_ratio = 1e-12 # max|Im| <= ratio max|Re|: a complex-step matrix, the dual-number path with the real factor (it
+                           # drops a term of relative order (cond ratio)^2; the complex-step matrices have ratio 1e-20);
+                           # above: full complex arithmetic through the real-equivalent factor
+
 # ---- restarted block Lanczos (lanczos.py)
 iram_block = 0             # block size (0: 8 for n >= 200 000, 4 for n >= 50 000, else the single-vector solver)
 iram_extra = None          # converged pairs beyond N kept for the adjoint stage's deflation (None: min(N, 32) with blocks)
