@@ -1013,7 +1013,7 @@ def _short_recurrence_applies(prob):
     if tuning.recurrence == "arnoldi" or fac is None or not fac.native:
         return False
     op = fac.factor
-    return not op._pivoted() and op._imag_dev is None and prob.opA.csr is not None and prob.opB.csr is not None
+    return not op.refined and not op.dual and prob.opA.csr is not None and prob.opB.csr is not None
 
 
 _CG_ROWS = {"rr": 0, "gam": 1, "rho": 2, "done": 3, "tol2": 4, "alpha": 5, "steps": 6, "flag": 7}

@@ -931,34 +931,31 @@ class DevicePanels:
         self.buf, other.buf = other.buf, self.buf
 
 
-class CSRMatrix:
-    """device copy of a scipy CSR matrix"""
+class _MatrixHandle:
+    """
+    Owner of one matrix handle of the library (CSRMatrix, ComplexCSRMatrix): upload, lifetime, the adjoint companion the
+    library makes from it once (the transposed / conjugate-transposed matrix), the product, new values and the numpy
+    surface, as host array -> block -> ``apply`` -> host array with the subclass's ``_to_block`` / ``_from_block``.
+    The subclass names the library's entry points (``_lib``) and how many block columns a column of an operand takes.
+    """
 
     def __init__(self, ctx, A):
         from scipy import sparse
 
         A = sparse.csr_matrix(A)
-        if A.dtype != np.float64:
-            A = A.astype(np.float64)
-        self.ctx = ctx
-        self.shape = A.shape
-        self.n, self.ncols = A.shape  # rectangular: the gather / averaging / filter maps of the design-variable chain
-        self.nnz = int(A.nnz)
+        if A.dtype != self.dtype:
+            A = A.astype(self.dtype)
         ip = np.ascontiguousarray(A.indptr, dtype=np.int32)
         ix = np.ascontiguousarray(A.indices, dtype=np.int32)
-        dv = np.ascontiguousarray(A.data, dtype=np.float64)
+        dv = np.ascontiguousarray(A.data, dtype=self.dtype)
         h = c_vp()
-        call("eigd_csr_upload_rect", ctx.h, self.n, self.ncols, self.nnz, hptr(ip), hptr(ix), hptr(dv), C.byref(h))
-        self.h = h
-        self._transposed = None
+        call(self._lib["upload"], ctx.h, *self._order(A.shape), int(A.nnz), hptr(ip), hptr(ix), hptr(dv), C.byref(h))
+        self._own(ctx, h, A.shape, int(A.nnz))
 
-    @classmethod
-    def _adopt(cls, ctx, h, shape, nnz):
-        """wrap a matrix the library made (the transposed companion)"""
-        self = cls.__new__(cls)
+    def _own(self, ctx, h, shape, nnz):
         self.ctx, self.h, self.shape, self.nnz = ctx, h, shape, nnz
         self.n, self.ncols = shape
-        self._transposed = None
+        self._companion = None
         return self
 
     def __del__(self):
@@ -969,43 +966,63 @@ class CSRMatrix:
         except Exception:
             pass
 
-    def transposed(self):
-        """
-        the device matrix of A^T (square matrices): made once from the pattern, ``apply`` is bit-identical to scipy's
-        ``A.T.tocsr() @ X``; ``update_values_device`` refreshes its values on the device
-        """
-        if self._transposed is None:
+    def adjoint(self):
+        """the device matrix of A^T (a complex matrix: A^H), square matrices: made once from the pattern;
+        ``update_values_device`` refreshes its values on the device"""
+        if self._companion is None:
             h = c_vp()
-            call("eigd_csr_transpose", self.h, C.byref(h))
-            self._transposed = CSRMatrix._adopt(self.ctx, h, (self.ncols, self.n), self.nnz)
-        return self._transposed
+            call(self._lib["adjoint"], self.h, C.byref(h))
+            self._companion = type(self).__new__(type(self))._own(self.ctx, h, (self.ncols, self.n), self.nnz)
+        return self._companion
 
     def apply(self, X, Y=None, alpha=1.0, beta=0.0):
-        """Y = alpha A X + beta Y"""
+        """
+        Y = alpha A X + beta Y on X's stream, alpha and beta real.  A complex matrix takes split-layout blocks (n x 2k:
+        real half, imaginary half)
+        """
+        if X.k % self._block_cols:
+            raise ValueError("a split-layout block has an even number of columns")
         if Y is None:
             Y = X.ctx.empty(self.n, X.k)
         if X.n != self.ncols or (Y.n, Y.k) != (self.n, X.k):
             raise ValueError("shape mismatch in SpMM")
-        call("eigd_spmm_on", X.ctx.h, self.h, X.ptr, X.ld, Y.ptr, Y.ld, X.k, float(alpha), float(beta))  # on X's stream
+        call(self._lib["spmm"], X.ctx.h, self.h, X.ptr, X.ld, Y.ptr, Y.ld, X.k // self._block_cols, float(alpha),
+             float(beta))
         return Y
 
-    dtype = np.dtype(np.float64)
+    def update_values_device(self, vals):
+        """new values, same sparsity: a device block in this matrix's CSR order, nnz doubles -- of a complex matrix
+        nnz x 2, contiguous: real and imaginary part per entry"""
+        if vals.n * vals.k < self._block_cols * self.nnz or (self._block_cols == 2 and vals.ld != vals.k):
+            raise ValueError("value count does not match the matrix")
+        call(self._lib["update"], self.h, vals.ptr)
+        if self._companion is not None:
+            call(self._lib["refresh"], self._companion.h, self.h)
 
     def matvec(self, x):
         """numpy in, numpy out: lets scipy's aslinearoperator wrap a matrix that lives on the device"""
-        x = np.asarray(x, dtype=np.float64)
-        out = self.apply(self.ctx.from_host(x.reshape(self.ncols, -1))).get()
+        x = np.asarray(x)
+        out = self._from_block(self.apply(self.ctx.from_host(self._to_block(x))).get())
         return out[:, 0] if x.ndim == 1 else out
 
     matmat = matvec
 
-    def update_values_device(self, vals):
-        """new values (device block of nnz doubles, in this matrix's CSR order), same sparsity"""
-        if vals.n * vals.k < self.nnz:
-            raise ValueError("value count does not match the matrix")
-        call("eigd_csr_update_values_dev", self.h, vals.ptr)
-        if self._transposed is not None:
-            call("eigd_csr_transpose_refresh", self._transposed.h, self.h)
+
+class CSRMatrix(_MatrixHandle):
+    """device copy of a scipy CSR matrix (rectangular too: the gather / averaging / filter maps of the design-variable
+    chain); ``transposed().apply`` is bit-identical to scipy's ``A.T.tocsr() @ X``"""
+
+    dtype = np.dtype(np.float64)
+    _block_cols = 1
+    _lib = {"upload": "eigd_csr_upload_rect", "adjoint": "eigd_csr_transpose", "spmm": "eigd_spmm_on",
+            "update": "eigd_csr_update_values_dev", "refresh": "eigd_csr_transpose_refresh"}
+    _order = staticmethod(lambda shape: shape)
+    transposed = _MatrixHandle.adjoint
+
+    def _to_block(self, x):
+        return np.asarray(x, dtype=np.float64).reshape(self.ncols, -1)
+
+    _from_block = staticmethod(lambda a: a)
 
     def spmv_bytes(self, k=1):
         """algorithmic bytes of one product"""
@@ -1128,71 +1145,24 @@ class ValueExpansion:
         return out
 
 
-class ComplexCSRMatrix:
+class ComplexCSRMatrix(_MatrixHandle):
     """
     device copy of a square complex scipy CSR matrix (interleaved complex values, one index list), applied to
     split-layout blocks: ``apply`` is bit-identical to scipy's complex ``A @ X``
     """
 
     dtype = np.dtype(np.complex128)
+    _block_cols = 2
+    _lib = {"upload": "eigd_ccsr_upload", "adjoint": "eigd_ccsr_conjugate_transpose", "spmm": "eigd_ccsr_spmm_on",
+            "update": "eigd_ccsr_update_values_dev", "refresh": "eigd_ccsr_conjugate_transpose_refresh"}
+    conjugate_transposed = _MatrixHandle.adjoint
+    _to_block, _from_block = staticmethod(complex_split), staticmethod(complex_join)
 
-    def __init__(self, ctx, A):
-        from scipy import sparse
-
-        A = sparse.csr_matrix(A).astype(np.complex128)
-        if A.shape[0] != A.shape[1]:
+    @staticmethod
+    def _order(shape):
+        if shape[0] != shape[1]:
             raise ValueError("expected a square matrix")
-        self.ctx = ctx
-        self.shape = A.shape
-        self.n = self.ncols = A.shape[0]
-        self.nnz = int(A.nnz)
-        ip = np.ascontiguousarray(A.indptr, dtype=np.int32)
-        ix = np.ascontiguousarray(A.indices, dtype=np.int32)
-        dv = np.ascontiguousarray(A.data, dtype=np.complex128)
-        h = c_vp()
-        call("eigd_ccsr_upload", ctx.h, self.n, self.nnz, hptr(ip), hptr(ix), hptr(dv), C.byref(h))
-        self.h = h
-        self._conjugate_transposed = None
-
-    __del__ = CSRMatrix.__del__
-
-    def conjugate_transposed(self):
-        """the device matrix of A^H: made once from the pattern; ``update_values_device`` refreshes its values on the device"""
-        if self._conjugate_transposed is None:
-            h = c_vp()
-            call("eigd_ccsr_conjugate_transpose", self.h, C.byref(h))
-            At = ComplexCSRMatrix.__new__(ComplexCSRMatrix)
-            At.ctx, At.h, At.shape, At.nnz, At.n, At.ncols = self.ctx, h, self.shape, self.nnz, self.n, self.n
-            At._conjugate_transposed = None
-            self._conjugate_transposed = At
-        return self._conjugate_transposed
-
-    def apply(self, X2, Y2=None, alpha=1.0, beta=0.0):
-        """Y = alpha A X + beta Y on split-layout blocks (n x 2k: real half, imaginary half); alpha, beta real"""
-        if X2.k % 2:
-            raise ValueError("a split-layout block has an even number of columns")
-        if Y2 is None:
-            Y2 = X2.ctx.empty(self.n, X2.k)
-        if X2.n != self.n or (Y2.n, Y2.k) != (self.n, X2.k):
-            raise ValueError("shape mismatch in SpMM")
-        call("eigd_ccsr_spmm_on", X2.ctx.h, self.h, X2.ptr, X2.ld, Y2.ptr, Y2.ld, X2.k // 2, float(alpha), float(beta))
-        return Y2
-
-    def matvec(self, x):
-        """numpy in, numpy out (complex128)"""
-        x = np.asarray(x)
-        out = complex_join(self.apply(self.ctx.from_host(complex_split(x))).get())
-        return out[:, 0] if x.ndim == 1 else out
-
-    matmat = matvec
-
-    def update_values_device(self, vals):
-        """new values (device block nnz x 2: real and imaginary part per entry, in this matrix's CSR order), same sparsity"""
-        if vals.n * vals.k < 2 * self.nnz or vals.ld != vals.k:
-            raise ValueError("value count does not match the matrix")
-        call("eigd_ccsr_update_values_dev", self.h, vals.ptr)
-        if self._conjugate_transposed is not None:
-            call("eigd_ccsr_conjugate_transpose_refresh", self._conjugate_transposed.h, self.h)
+        return shape[:1]
 
     def spmm_bytes(self, k=1):
         """algorithmic bytes of one product with k complex columns"""
@@ -1333,6 +1303,24 @@ def symmetrised_pattern(A):
     return sparse.csr_matrix((vals, M.indices, M.indptr), shape=A.shape)
 
 
+def refine(raw_solve, matrix, B, X, alpha=1.0, steps=1):
+    """
+    X <- X + M^{-1} (alpha B - M X), ``steps`` times: iterative refinement of X ~ alpha M^{-1} B on device blocks, all on
+    X's context.  ``raw_solve(R)`` solves with the factor alone in place on a block; ``matrix.apply(X, R)`` is the
+    product with the true M (its adjoint companion where ``raw_solve`` is the transposed solve; ``matrix`` may be the
+    bound method that makes it, called once the work block is there).
+    """
+    R = X.ctx.empty(X.n, X.k)
+    if callable(matrix):
+        matrix = matrix()
+    for _ in range(steps):
+        matrix.apply(X, R)
+        R.assign_lincomb([(alpha, B), (-1.0, R)])
+        raw_solve(R)
+        X.assign_lincomb([(1.0, X), (1.0, R)])
+    return X
+
+
 class Factor:
     """
     Numeric factor of a CSR matrix on the device: L S L^T of a symmetric matrix (Cholesky, Bunch-Kaufman inside the
@@ -1386,15 +1374,8 @@ class Factor:
         X <- X + mat^{-1} (alpha B - mat X), ``steps`` times: iterative refinement of X ~ alpha mat^{-1} B on device blocks
         (``trans``: of X ~ alpha mat^{-T} B, residual with the transposed companion of ``mat_dev``)
         """
-        R = X.ctx.empty(X.n, X.k)
-        if trans:
-            mat_dev = mat_dev.transposed()
-        for _ in range(steps):
-            mat_dev.apply(X, R)
-            R.assign_lincomb([(alpha, B), (-1.0, R)])
-            self.solve_to(R, R, 1.0, trans=trans)
-            X.assign_lincomb([(1.0, X), (1.0, R)])
-        return X
+        return refine(lambda R: self.solve_to(R, R, 1.0, trans=trans), mat_dev.transposed if trans else mat_dev,
+                      B, X, alpha, steps)
 
     STATIC_PIVOT_REFINEMENTS = 3
 

@@ -973,7 +973,7 @@ def _solve_complex_step(self, A, B, factor, sigma, n):
     """
     from scipy import sparse
 
-    if not (isinstance(factor, SpLuOperator) and factor._imag_dev is not None):
+    if not (isinstance(factor, SpLuOperator) and factor.dual):
         raise TypeError("the complex-step path needs an eigd_amd.SpLuOperator built on the complex shifted matrix")
     if not sparse.issparse(B):
         raise TypeError("the complex-step path needs B as a scipy sparse matrix")

@@ -11,7 +11,8 @@ from scipy.sparse.linalg import LinearOperator
 
 from . import tuning
 from .device import (ComplexCSRMatrix, CSRMatrix, DeviceBlock, Factor, ValueExpansion, complex_join, complex_split,
-                     default_context, expand_values_host, interleaved_view, real_equivalent_pattern, symmetrised_pattern)
+                     default_context, expand_values_host, interleaved_view, real_equivalent_pattern, refine,
+                     symmetrised_pattern)
 
 COMPLEX_ARITHMETIC = ("auto", "dual", "full")
 
@@ -31,23 +32,6 @@ def select_complex_arithmetic(data, requested="auto"):
     return "dual" if np.max(np.abs(data.imag)) <= tuning.complex_step_ratio * np.max(np.abs(data.real)) else "full"
 
 
-class _RealEquivalentOfComplex:
-    """the real-equivalent matrix of a device complex matrix, applied to 2n x k blocks (Factor.verify_static_pivots)"""
-
-    def __init__(self, cmat, form):
-        self.cmat, self.form = cmat, form
-
-    def apply(self, X, Y=None):
-        if Y is None:
-            Y = X.ctx.empty(X.n, X.k)
-        Y2 = DeviceBlock(Y.ctx, Y.n // 2, 2 * Y.k, Y.buf, Y.offset, 2 * Y.k)
-        self.cmat.apply(DeviceBlock(X.ctx, X.n // 2, 2 * X.k, X.buf, X.offset, 2 * X.k), Y2)
-        if self.form == "symmetric":  # (its second block row is the negated one)
-            im = Y2.cols(Y.k, 2 * Y.k)
-            im.assign_lincomb([(-1.0, im)])
-        return Y
-
-
 def _with_structural_diagonal(csr):
     """
     The symbolic analysis needs every diagonal entry stored.  A shift that annihilates one exactly (sigma = K_pp / M_pp:
@@ -65,6 +49,284 @@ def _with_structural_diagonal(csr):
                              (np.concatenate([coo.row, miss]), np.concatenate([coo.col, miss]))), shape=csr.shape)
     out.sort_indices()
     return out
+
+
+def _check_symmetric(whole, parts):
+    """``parts`` (the real matrix, or the real and the imaginary part of a complex one) against a random vector"""
+    x = np.random.default_rng(0).uniform(-1.0, 1.0, size=whole.shape[0])
+    for part in parts:
+        d = part @ x - part.T @ x
+        if np.linalg.norm(d) > 1e-10 * max(np.linalg.norm(whole @ x), 1e-300):
+            raise ValueError("SpLuOperator (MI355X) needs a symmetric matrix; pass symmetric=False for an LU factor")
+
+
+def complex_application(kind, trans, conjugate):
+    """
+    How a full-complex factor of ``kind`` applies mat^{-1} (``trans``: mat^{-T}; with ``conjugate`` as well: mat^{-H};
+    ``conjugate`` alone: conj(mat)^{-1}): (herm, wrap) -- the raw solve is mat^{-H} instead of mat^{-1}; the right-hand
+    side is conjugated before and the solution after
+    """
+    if kind == "lu":
+        return bool(trans), bool(trans) != bool(conjugate)      # mat^{-T} = conj o mat^{-H} o conj
+    return bool(conjugate), False                               # mat = mat^T
+
+
+class _Backend:
+    """
+    What SpLuOperator needs of one arithmetic: the ``factor``, the raw solve with it (``raw``), the ``matrix`` of the
+    refinement's residuals (with its adjoint companion), ``refactor`` / ``refactor_device`` and the way of a host array
+    through the operator's device surface (``apply_host``).  ``solve`` is the one refined solve over them.
+    """
+
+    complex_arithmetic = None
+    refined = True                   # (the real backend knows better: a positive definite matrix needs no refinement)
+    negative_pivots = negative_pivots_bounds = None     # (no inertia but from a real symmetric factor)
+
+    def _read_factor(self):
+        """after every numeric phase: the figures SpLuOperator shows, and how often applications are refined"""
+        st = self.factor.stats()
+        self.kind, self.row_interchanges = st["kind"], st["row_interchanges"]
+        self.static_pivots = st["static_pivots"]   # pivots singular inside their panel block, replaced by +-sqrt(eps)|A|
+        self.steps = self.factor.STATIC_PIVOT_REFINEMENTS if self.static_pivots > 0 else 1
+        return st
+
+    def solve(self, X, alpha=1.0, Xin=None, adjoint=False):
+        """
+        X <- alpha mat^{-1} Xin (``Xin`` None: in place; ``adjoint``: with the transposed / conjugate-transposed matrix),
+        refined against ``matrix`` where there is one: one step, three with static pivots.  Everything on X's context:
+        with concurrent mode groups (streams > 1) X lives on a forked context whose stream and sweep lane must carry
+        the whole application
+        """
+        if self.matrix is None:
+            return self.raw(Xin, X, alpha, adjoint)
+        B = X.copy() if Xin is None else Xin
+        self.raw(Xin, X, alpha, adjoint)
+        return refine(lambda R: self.raw(R, R, 1.0, adjoint), self.matrix.adjoint if adjoint else self.matrix, B, X,
+                      alpha, self.steps)
+
+    def solve_complex(self, Xr, Xi, trans, conjugate, counted):
+        raise TypeError("solve_device_dual needs an operator built on a complex (complex-step) matrix")
+
+
+class _RealBackend(_Backend):
+    """
+    The LDL^T or LU factor of a real matrix.  ``matrix`` is None where no refinement is due (a positive definite
+    matrix); an indefinite or LU factor pivots inside its panels only, and every application is refined.
+    """
+
+    def __init__(self, ctx, csr, request, symmetric, check_symmetry, **analysis):
+        self.ctx, self.request = ctx, request
+        csr = csr.astype(np.float64)  # for a symmetric matrix CSC and CSR coincide
+        csr.sort_indices()
+        if symmetric:  # (the LU factor symmetrises the pattern itself; the refinement applies csr as it is)
+            csr = _with_structural_diagonal(csr)
+            if check_symmetry:
+                _check_symmetric(csr, (csr,))
+        self.factor = Factor(ctx, csr, lu=not symmetric, **analysis)
+        self._read_factor()
+        self.matrix = CSRMatrix(ctx, csr) if self.refined else None
+
+    def raw(self, Xin, X, alpha, trans):
+        if Xin is None:
+            return self.factor.solve_inplace(X, alpha, trans=trans)
+        return self.factor.solve_to(Xin, X, alpha, trans=trans)
+
+    def _read_factor(self):
+        st = super()._read_factor()
+        # (an LU factor pivots inside its panels only: always refined, and it gives no inertia)
+        self.refined = self.kind == "lu" or st["negative_pivots"] > 0 or self.static_pivots > 0
+        if self.kind != "lu":
+            self.negative_pivots = st["negative_pivots"]
+            # a static pivot takes its sign from a diagonal entry at rounding level: the inertia is then known only up
+            # to their number -- negative_pivots_bounds brackets the count of eigenvalues below the shift
+            self.negative_pivots_bounds = (max(0, self.negative_pivots - self.static_pivots),
+                                           self.negative_pivots + self.static_pivots)
+
+    def solve(self, X, alpha=1.0, Xin=None, adjoint=False):
+        # (a symmetric matrix is its own transpose)
+        return super().solve(X, alpha, Xin, bool(adjoint) and self.kind == "lu")
+
+    def refactor(self, mat):
+        if np.issubdtype(mat.dtype, np.complexfloating) and select_complex_arithmetic(
+                mat.tocsr().data, "dual" if self.request == "dual" else "auto") == "full":
+            raise ValueError("this operator was not built for full complex arithmetic: make a new one for this matrix")
+        csr = mat.tocsr().astype(np.float64)
+        csr.sort_indices()
+        self.factor.refactor(csr)
+        self._read_factor()
+        self.matrix = CSRMatrix(self.ctx, csr) if self.refined else None
+
+    def refactor_device(self, vals, indefinite_matrix):
+        self.factor.refactor_device(vals)
+        self._read_factor()
+        if self.refined and indefinite_matrix is None:
+            raise ValueError("indefinite refactorisation: pass the device matrix for the refinement step")
+        self.matrix = indefinite_matrix if self.refined else None
+        if self.static_pivots > 0:
+            self.factor.verify_static_pivots(self.matrix)
+
+    def apply_host(self, op, x, adjoint):
+        return op.solve_device(self.ctx.from_host(x.astype(np.float64)), trans=adjoint).get()
+
+
+class _DualBackend(_RealBackend):
+    """
+    Complex-step matrices (reference 11-23 with a complex mat): mat = M + i dM with dM ~ 1e-20 M is a dual
+    number -- products of two imaginary parts vanish below rounding -- so mat^{-1}(b + i db) = x + i M^{-1}(db - dM x)
+    with x = M^{-1} b: the real backend of M, applied twice, and the device matrix of dM.
+    """
+
+    complex_arithmetic = "dual"
+
+    def __init__(self, ctx, cm, *args, **analysis):
+        self.imag = CSRMatrix(ctx, sparse.csr_matrix((cm.data.imag.copy(), cm.indices, cm.indptr), shape=cm.shape))
+        super().__init__(ctx, sparse.csr_matrix((cm.data.real.copy(), cm.indices, cm.indptr), shape=cm.shape), *args,
+                         **analysis)
+
+    def solve_complex(self, Xr, Xi, trans, conjugate, counted):
+        counted()
+        self.solve(Xr, adjoint=trans)
+        T = (self.imag.transposed() if trans else self.imag).apply(Xr)
+        Xi.assign_lincomb([(1.0, Xi), (1.0 if conjugate else -1.0, T)])
+        self.solve(Xi, adjoint=trans)
+
+    def apply_host(self, op, x, adjoint):
+        xc = x.astype(np.complex128)
+        Xr, Xi = op.solve_device_dual(self.ctx.from_host(np.ascontiguousarray(xc.real)),
+                                      self.ctx.from_host(np.ascontiguousarray(xc.imag)), trans=adjoint, conjugate=adjoint)
+        return Xr.get() + 1j * Xi.get()
+
+
+class _FullComplexBackend(_Backend):
+    """
+    True complex arithmetic through the real-equivalent system of order 2n with interleaved unknowns: the LU factor of
+    the form [[a, -b], [b, a]] per entry, or for a complex symmetric matrix the Bunch-Kaufman factor of
+    [[a, -b], [-b, -a]].  A complex block is n x 2k (real half, imaginary half): the memory of the 2n x k block the
+    factor takes.  Every application is refined against the complex matrix itself (``matrix``).
+    """
+
+    complex_arithmetic = "full"
+
+    def __init__(self, ctx, cm, request, symmetric, check_symmetry, coords=None, **analysis):
+        self.ctx, self.symmetric = ctx, symmetric
+        cm = self._canonical_complex(cm)
+        if check_symmetry and symmetric:
+            _check_symmetric(cm, (cm.real.tocsr(), cm.imag.tocsr()))
+        req, self._table = self._real_equivalent_of(cm)
+        self._pattern = (cm.indptr.copy(), cm.indices.copy())
+        self._expansion = None
+        if coords is not None:  # both unknowns of a dof sit at its node
+            coords = np.repeat(np.asarray(coords, dtype=np.float64).reshape(cm.shape[0], -1), 2, axis=0)
+        self.factor = Factor(ctx, req, coords=coords, lu=not symmetric, **analysis)
+        self._read_factor()
+        self.matrix = ComplexCSRMatrix(ctx, cm)
+
+    def _real_equivalent_of(self, cm):
+        """(real-equivalent CSR matrix of the canonical complex CSR matrix ``cm``, expansion table): on the pattern the
+        factor is analysed on -- symmetrised for the LU form, with every diagonal entry for the symmetric form"""
+        n = cm.shape[0]
+        # where the entries of cm sit in that pattern: the pattern helpers carry the entry numbers along as values
+        numbered = sparse.csr_matrix((np.arange(1.0, cm.nnz + 1.0), cm.indices, cm.indptr), shape=cm.shape)
+        padded = _with_structural_diagonal(numbered) if self.symmetric else symmetrised_pattern(numbered)
+        source = padded.data.astype(np.int64) - 1
+        ip2, ix2, table = real_equivalent_pattern(padded.indptr, padded.indices, "symmetric" if self.symmetric else "lu",
+                                                  source)
+        return sparse.csr_matrix((expand_values_host(table, cm.data), ix2, ip2), shape=(2 * n, 2 * n)), table
+
+    @staticmethod
+    def _canonical_complex(mat):
+        cm = sparse.csr_matrix(mat).astype(np.complex128)
+        if not cm.has_canonical_format:
+            cm = cm.copy()
+            cm.sum_duplicates()
+        return cm
+
+    def raw(self, Xin, Z, alpha, herm):
+        """Z <- alpha mat^{-1} Xin (``herm``: mat^{-H}; ``Xin`` None: Z) with the factor alone, on contiguous split-layout
+        blocks: the factor works in place on Z"""
+        if Xin is not None and Xin is not Z:
+            Z.copy_from(Xin)
+        k = Z.k // 2
+        im = Z.cols(k, 2 * k)
+        V = interleaved_view(Z)
+        if not self.symmetric:  # (the transposed real-equivalent matrix is the real-equivalent of mat^H)
+            return self.factor.solve_to(V, V, alpha, trans=herm)
+        # symmetric form [[Ar, -Ai], [-Ai, -Ar]] (xr, xi) = (br, -bi); mat^{-H} = conj o mat^{-1} o conj for mat = mat^T: the
+        # conjugation of the right-hand side and the sign of the form cancel, the solution is conjugated instead
+        if not herm:
+            im.assign_lincomb([(-1.0, im)])
+        self.factor.solve_to(V, V, alpha)
+        if herm:
+            im.assign_lincomb([(-1.0, im)])
+        return Z
+
+    def solve_complex(self, Xr, Xi, trans, conjugate, counted):
+        k = Xr.k
+        if (Xi.n, Xi.k) != (Xr.n, k) or 2 * Xr.n != self.factor.n:
+            raise ValueError("shape mismatch in the complex solve")
+        counted()
+        halves = Xr.buf is Xi.buf and Xr.ld == Xi.ld == 2 * k and Xi.offset == Xr.offset + k
+        if halves:
+            Z = DeviceBlock(Xr.ctx, Xr.n, 2 * k, Xr.buf, Xr.offset, 2 * k)
+        else:
+            Z = Xr.ctx.empty(Xr.n, 2 * k)
+            Z.cols(0, k).copy_from(Xr)
+            Z.cols(k, 2 * k).copy_from(Xi)
+        herm, wrap = complex_application(self.kind, trans, conjugate)
+        im = Z.cols(k, 2 * k)
+        if wrap:
+            im.assign_lincomb([(-1.0, im)])
+        self.solve(Z, adjoint=herm)
+        if wrap:
+            im.assign_lincomb([(-1.0, im)])
+        if not halves:
+            Xr.copy_from(Z.cols(0, k))
+            Xi.copy_from(Z.cols(k, 2 * k))
+
+    def refactor(self, mat):
+        if not np.issubdtype(mat.dtype, np.complexfloating):
+            raise ValueError("this operator works in full complex arithmetic: refactor it with a complex matrix")
+        cm = self._canonical_complex(mat)
+        if not (np.array_equal(cm.indptr, self._pattern[0]) and np.array_equal(cm.indices, self._pattern[1])):
+            raise ValueError("the complex matrix has a different sparsity pattern")
+        req, _ = self._real_equivalent_of(cm)
+        self.factor.refactor(req)
+        self._read_factor()
+        self.matrix = ComplexCSRMatrix(self.ctx, cm)
+
+    def expand_values_device(self, vals):
+        if self._expansion is None:
+            self._expansion = ValueExpansion(self.ctx, self._table, len(self._pattern[1]))
+        return self._expansion.expand(vals)
+
+    def apply(self, X, Y=None):
+        """the matrix the factor factors: the real-equivalent one of ``matrix``, applied to 2n x k blocks
+        (Factor.verify_static_pivots takes the backend for it)"""
+        if Y is None:
+            Y = X.ctx.empty(X.n, X.k)
+        Y2 = DeviceBlock(Y.ctx, Y.n // 2, 2 * Y.k, Y.buf, Y.offset, 2 * Y.k)
+        self.matrix.apply(DeviceBlock(X.ctx, X.n // 2, 2 * X.k, X.buf, X.offset, 2 * X.k), Y2)
+        if self.symmetric:  # (its second block row is the negated one)
+            im = Y2.cols(Y.k, 2 * Y.k)
+            im.assign_lincomb([(-1.0, im)])
+        return Y
+
+    def refactor_device(self, vals, indefinite_matrix):
+        if indefinite_matrix is not None and not isinstance(indefinite_matrix, ComplexCSRMatrix):
+            raise TypeError("full complex arithmetic: the refinement needs a ComplexCSRMatrix")
+        self.factor.refactor_device(self.expand_values_device(vals))
+        self._read_factor()
+        if indefinite_matrix is not None:
+            self.matrix = indefinite_matrix
+        else:                        # (every application is refined: the operator's own matrix takes the new values)
+            self.matrix.update_values_device(vals)
+        if self.static_pivots > 0:
+            self.factor.verify_static_pivots(self)
+
+    def apply_host(self, op, x, adjoint):
+        Z = self.ctx.from_host(complex_split(x))
+        op.solve_device_dual(Z.cols(0, Z.k // 2), Z.cols(Z.k // 2, Z.k), trans=adjoint, conjugate=adjoint)
+        return complex_join(Z.get())
 
 
 class SpLuOperator(LinearOperator):
@@ -109,6 +371,14 @@ class SpLuOperator(LinearOperator):
     ``max|Im| <= tuning.complex_step_ratio max|Re|`` (1e-12; complex-step perturbations are of relative size 1e-20)
     and ``"full"`` otherwise.  In ``"full"`` mode ``op.H`` applies ``mat^{-H}`` and ``op.T`` ``mat^{-T}``;
     ``solve_device_dual`` is the complex solve on device blocks and ``solve_device`` / ``solve_device_to`` raise.
+
+    Structure: the constructor chooses one backend per arithmetic (``_RealBackend``, ``_DualBackend`` -- the real one
+    plus the imaginary-part matrix --, ``_FullComplexBackend``).  A backend owns the factor, the matrix of the
+    refinement's residuals, the raw solve, the refactorisations and the layout of a host array on the device; every
+    application is ``_Backend.solve``, the one refined solve, over ``device.refine``.  The operator keeps the counter,
+    the scipy surface and read-only views of the factor's figures (``kind``, the inertia, ...).  ``refined`` tells
+    whether applications are refined (an indefinite, LU or full-complex factor), ``dual`` whether the operator is a
+    complex-step one.
     """
 
     def __init__(self, mat, ctx=None, symbolic=None, leaf_size=0, panel_width=0, check_symmetry=True, coords=None,
@@ -124,178 +394,39 @@ class SpLuOperator(LinearOperator):
         self.dtype = np.dtype(np.float64)
         self.count = 0
         self._count_lock = threading.Lock()  # mode groups on different streams share the counter
-        # Complex-step matrices (reference 11-23 with a complex mat): mat = M + i dM with dM ~ 1e-20 M is a
-        # dual number -- products of two imaginary parts vanish below rounding -- so mat^{-1}(b + i db) =
-        # x + i M^{-1}(db - dM x) with x = M^{-1} b: the real factor, applied twice.
-        self._imag_dev = None
-        self._cmat_dev = None            # "full": the complex matrix itself (the refinement's residuals)
-        self.complex_arithmetic = None
-        self._complex_request = complex_arithmetic
         self.symmetric = bool(symmetric)
+        csr = mat.tocsr()
+        backend = _RealBackend
         if np.issubdtype(mat.dtype, np.complexfloating):
-            cm = mat.tocsr()
-            cm.sort_indices()
+            csr.sort_indices()
             self.dtype = np.dtype(np.complex128)
-            self.complex_arithmetic = select_complex_arithmetic(cm.data, complex_arithmetic)
-            if self.complex_arithmetic == "full":
-                self._init_full(cm, symbolic, leaf_size, panel_width, check_symmetry, coords)
-                return
-            self._imag_dev = CSRMatrix(self.ctx, sparse.csr_matrix((cm.data.imag.copy(), cm.indices, cm.indptr), shape=cm.shape))
-            mat = sparse.csr_matrix((cm.data.real.copy(), cm.indices, cm.indptr), shape=cm.shape)
-        csr = mat.tocsr().astype(np.float64)  # for a symmetric matrix CSC and CSR coincide
-        csr.sort_indices()
-        if self.symmetric:  # (the LU factor symmetrises the pattern itself; the refinement applies csr as it is)
-            csr = _with_structural_diagonal(csr)
-        if check_symmetry and self.symmetric:
-            x = np.random.default_rng(0).uniform(-1.0, 1.0, size=csr.shape[0])
-            d = csr @ x - csr.T @ x
-            if np.linalg.norm(d) > 1e-10 * max(np.linalg.norm(csr @ x), 1e-300):
-                raise ValueError("SpLuOperator (MI355X) needs a symmetric matrix; pass symmetric=False for an LU factor")
+            full = select_complex_arithmetic(csr.data, complex_arithmetic) == "full"
+            backend = _FullComplexBackend if full else _DualBackend
         # coords (optional, one row per dof): geometric nested dissection; without it the ordering is algebraic
-        self.factor = Factor(self.ctx, csr, symbolic=symbolic, leaf_size=leaf_size, panel_width=panel_width,
-                             coords=coords, lu=not self.symmetric)
+        self._backend = backend(self.ctx, csr, complex_arithmetic, self.symmetric, check_symmetry, symbolic=symbolic,
+                                leaf_size=leaf_size, panel_width=panel_width, coords=coords)
+        self.complex_arithmetic = backend.complex_arithmetic
+        self.factor = self._backend.factor
         self.symbolic = self.factor.symbolic
-        self._read_inertia()
-        # indefinite: pivoting is confined to the panel blocks -> one refinement step per application (three when static
-        # pivots were needed)
-        self._mat_dev = CSRMatrix(self.ctx, csr) if self._pivoted() else None
 
-    # -- full complex arithmetic: the real-equivalent factor -----------------------------------------------------------
-    def _real_equivalent_of(self, cm):
-        """(real-equivalent CSR matrix of the canonical complex CSR matrix ``cm``, expansion table): on the pattern the
-        factor is analysed on -- symmetrised for the LU form, with every diagonal entry for the symmetric form"""
-        n = cm.shape[0]
-        # where the entries of cm sit in that pattern: the pattern helpers carry the entry numbers along as values
-        numbered = sparse.csr_matrix((np.arange(1.0, cm.nnz + 1.0), cm.indices, cm.indptr), shape=cm.shape)
-        padded = _with_structural_diagonal(numbered) if self.symmetric else symmetrised_pattern(numbered)
-        source = padded.data.astype(np.int64) - 1
-        ip2, ix2, table = real_equivalent_pattern(padded.indptr, padded.indices, "symmetric" if self.symmetric else "lu",
-                                                  source)
-        return sparse.csr_matrix((expand_values_host(table, cm.data), ix2, ip2), shape=(2 * n, 2 * n)), table
-
-    @staticmethod
-    def _canonical_complex(mat):
-        cm = sparse.csr_matrix(mat).astype(np.complex128)
-        if not cm.has_canonical_format:
-            cm = cm.copy()
-            cm.sum_duplicates()
-        return cm
-
-    def _init_full(self, cm, symbolic, leaf_size, panel_width, check_symmetry, coords):
-        cm = self._canonical_complex(cm)
-        if check_symmetry and self.symmetric:
-            x = np.random.default_rng(0).uniform(-1.0, 1.0, size=cm.shape[0])
-            for part in (cm.real.tocsr(), cm.imag.tocsr()):
-                d = part @ x - part.T @ x
-                if np.linalg.norm(d) > 1e-10 * max(np.linalg.norm(cm @ x), 1e-300):
-                    raise ValueError("SpLuOperator (MI355X) needs a symmetric matrix; pass symmetric=False for an LU factor")
-        req, self._table = self._real_equivalent_of(cm)
-        self._pattern = (cm.indptr.copy(), cm.indices.copy())
-        self._expansion = None
-        if coords is not None:  # both unknowns of a dof sit at its node
-            coords = np.repeat(np.asarray(coords, dtype=np.float64).reshape(cm.shape[0], -1), 2, axis=0)
-        self.factor = Factor(self.ctx, req, symbolic=symbolic, leaf_size=leaf_size, panel_width=panel_width,
-                             coords=coords, lu=not self.symmetric)
-        self.symbolic = self.factor.symbolic
-        self._read_inertia()
-        self._mat_dev = None
-        self._cmat_dev = ComplexCSRMatrix(self.ctx, cm)
-
-    def _raw_full(self, Z, herm):
-        """Z <- mat^{-1} Z (``herm``: mat^{-H} Z) with the factor alone, in place on a contiguous split-layout block"""
-        k = Z.k // 2
-        im = Z.cols(k, 2 * k)
-        V = interleaved_view(Z)
-        if self.kind == "lu":  # (the transposed real-equivalent matrix is the real-equivalent of mat^H)
-            return self.factor.solve_to(V, V, 1.0, trans=herm)
-        # symmetric form [[Ar, -Ai], [-Ai, -Ar]] (xr, xi) = (br, -bi); mat^{-H} = conj o mat^{-1} o conj for mat = mat^T: the
-        # conjugation of the right-hand side and the sign of the form cancel, the solution is conjugated instead
-        if not herm:
-            im.assign_lincomb([(-1.0, im)])
-        self.factor.solve_to(V, V, 1.0)
-        if herm:
-            im.assign_lincomb([(-1.0, im)])
-        return Z
-
-    def _solve_full(self, Z, trans=False, conjugate=False):
-        """
-        Z <- mat^{-1} Z in place on a contiguous split-layout block (n x 2k), refined against the complex matrix;
-        ``trans``: mat^{-T}, with ``conjugate`` as well: mat^{-H}; ``conjugate`` alone: conj(mat)^{-1}
-        """
-        if self.kind == "lu":
-            herm, wrap = bool(trans), bool(trans) != bool(conjugate)   # mat^{-T} = conj o mat^{-H} o conj
-        else:
-            herm, wrap = bool(conjugate), False                         # mat = mat^T
-        k = Z.k // 2
-        im = Z.cols(k, 2 * k)
-        if wrap:
-            im.assign_lincomb([(-1.0, im)])
-        B = Z.copy()
-        self._raw_full(Z, herm)
-        M = self._cmat_dev.conjugate_transposed() if herm else self._cmat_dev
-        R = Z.ctx.empty(Z.n, Z.k)
-        for _ in range(self._refine_steps):
-            M.apply(Z, R)
-            R.assign_lincomb([(1.0, B), (-1.0, R)])
-            self._raw_full(R, herm)
-            Z.assign_lincomb([(1.0, Z), (1.0, R)])
-        if wrap:
-            im.assign_lincomb([(-1.0, im)])
-        return Z
-
-    def _refactor_full(self, mat):
-        if not np.issubdtype(mat.dtype, np.complexfloating):
-            raise ValueError("this operator works in full complex arithmetic: refactor it with a complex matrix")
-        cm = self._canonical_complex(mat)
-        if not (np.array_equal(cm.indptr, self._pattern[0]) and np.array_equal(cm.indices, self._pattern[1])):
-            raise ValueError("the complex matrix has a different sparsity pattern")
-        req, _ = self._real_equivalent_of(cm)
-        self.factor.refactor(req)
-        self._read_inertia()
-        self._cmat_dev = ComplexCSRMatrix(self.ctx, cm)
+    # the factor's figures and whether applications are refined: the backend's, as of its last numeric phase
+    kind = property(lambda self: self._backend.kind)
+    row_interchanges = property(lambda self: self._backend.row_interchanges)
+    static_pivots = property(lambda self: self._backend.static_pivots)
+    negative_pivots = property(lambda self: self._backend.negative_pivots)
+    negative_pivots_bounds = property(lambda self: self._backend.negative_pivots_bounds)
+    refined = property(lambda self: self._backend.refined)
+    _pivoted = refined.fget          # (the name the drivers used to read)
+    dual = property(lambda self: self.complex_arithmetic == "dual")
+    _real_equivalent_of = _FullComplexBackend._real_equivalent_of   # (test_complex_cpu.py restates the tables through it)
 
     def expand_values_device(self, vals):
         """("full") the real-equivalent CSR values the factor takes, from complex values on the device (nnz x 2 block)"""
-        if self._expansion is None:
-            self._expansion = ValueExpansion(self.ctx, self._table, len(self._pattern[1]))
-        return self._expansion.expand(vals)
+        return self._backend.expand_values_device(vals)
 
-    def _refactor_device_full(self, vals, indefinite_matrix):
-        if indefinite_matrix is not None and not isinstance(indefinite_matrix, ComplexCSRMatrix):
-            raise TypeError("full complex arithmetic: the refinement needs a ComplexCSRMatrix")
-        self.factor.refactor_device(self.expand_values_device(vals))
-        self._read_inertia()
-        if indefinite_matrix is not None:
-            self._cmat_dev = indefinite_matrix
-        else:                        # (every application is refined: the operator's own matrix takes the new values)
-            self._cmat_dev.update_values_device(vals)
-        if self.static_pivots > 0:
-            self.factor.verify_static_pivots(_RealEquivalentOfComplex(self._cmat_dev, "lu" if self.kind == "lu" else "symmetric"))
-
-    def _pivoted(self):
-        # (an LU factor pivots inside its panels only: always refined; so is every full-complex application)
-        return self.complex_arithmetic == "full" or self.kind == "lu" or self.negative_pivots > 0 or self.static_pivots > 0
-
-    def _read_inertia(self):
-        st = self.factor.stats()
-        self.kind = st["kind"]
-        self.row_interchanges = st["row_interchanges"]
-        self.static_pivots = st["static_pivots"]   # pivots singular inside their panel block, replaced by +-sqrt(eps)|A|
-        self._refine_steps = self.factor.STATIC_PIVOT_REFINEMENTS if self.static_pivots > 0 else 1
-        if self.kind == "lu" or self.complex_arithmetic == "full":  # no inertia (the symmetric real-equivalent form: always (n, n))
-            self.negative_pivots = self.negative_pivots_bounds = None
-            return
-        self.negative_pivots = st["negative_pivots"]
-        # a static pivot takes its sign from a diagonal entry at rounding level: the inertia is then known only up to
-        # their number -- negative_pivots_bounds brackets the count of eigenvalues below the shift
-        self.negative_pivots_bounds = (max(0, self.negative_pivots - self.static_pivots),
-                                       self.negative_pivots + self.static_pivots)
-
-    def _refine(self, B, X, alpha, trans=False):
-        """X <- X + mat^{-1} (alpha B - mat X): iterative refinement on device blocks (one step; three with static pivots)"""
-        # everything on X's context: with concurrent mode groups (streams > 1) X lives on a forked context whose
-        # stream and sweep lane must carry the whole refinement step
-        return self.factor.refine(self._mat_dev, B, X, alpha, steps=self._refine_steps, trans=trans)
+    def _counted(self, k, count):
+        with self._count_lock:
+            self.count += k if count is None else int(count)
 
     # -- device path (used by the drivers) ------------------------------------
     def solve_device(self, X, alpha=1.0, count=None, trans=False):
@@ -305,14 +436,8 @@ class SpLuOperator(LinearOperator):
         the counter then means what the reference's does: applications per mode (ref 19-22).
         """
         self._no_real_block("solve_device")
-        trans = bool(trans) and self.kind == "lu"  # (a symmetric matrix is its own transpose)
-        with self._count_lock:
-            self.count += X.k if count is None else int(count)
-        if self._mat_dev is None:
-            return self.factor.solve_inplace(X, alpha, trans=trans)
-        B = X.copy()
-        self.factor.solve_inplace(X, alpha, trans=trans)
-        return self._refine(B, X, alpha, trans)
+        self._counted(X.k, count)
+        return self._backend.solve(X, alpha, adjoint=trans)
 
     def _no_real_block(self, name):
         if self.complex_arithmetic == "full":
@@ -321,13 +446,8 @@ class SpLuOperator(LinearOperator):
     def solve_device_to(self, Xin, Xout, alpha=1.0, count=None, trans=False):
         """Xout <- alpha * mat^{-1} Xin on device blocks, Xin untouched (``trans``: alpha * mat^{-T} Xin)"""
         self._no_real_block("solve_device_to")
-        trans = bool(trans) and self.kind == "lu"
-        with self._count_lock:
-            self.count += Xin.k if count is None else int(count)
-        self.factor.solve_to(Xin, Xout, alpha, trans=trans)
-        if self._mat_dev is not None:
-            self._refine(Xin, Xout, alpha, trans)
-        return Xout
+        self._counted(Xin.k, count)
+        return self._backend.solve(Xout, alpha, Xin, adjoint=trans)
 
     def refactor_device(self, vals, indefinite_matrix=None):
         """
@@ -337,81 +457,27 @@ class SpLuOperator(LinearOperator):
         arithmetic: ``vals`` is an nnz x 2 block (real and imaginary part per entry, CSR order of the matrix the operator
         was built on), ``indefinite_matrix`` a ComplexCSRMatrix holding them (None: the operator's own takes them).
         """
-        if self.complex_arithmetic == "full":
-            return self._refactor_device_full(vals, indefinite_matrix)
-        self.factor.refactor_device(vals)
-        self._read_inertia()
-        if self._pivoted() and indefinite_matrix is None:
-            raise ValueError("indefinite refactorisation: pass the device matrix for the refinement step")
-        self._mat_dev = indefinite_matrix if self._pivoted() else None
-        if self.static_pivots > 0:
-            self.factor.verify_static_pivots(self._mat_dev)
+        self._backend.refactor_device(vals, indefinite_matrix)
 
     def refactor(self, mat):
         """numeric refactorisation with new values on the same sparsity pattern (a complex matrix stays on the path --
         ``complex_arithmetic`` -- the operator was built on: switching between "dual" and "full" raises)"""
-        if self.complex_arithmetic == "full":
-            return self._refactor_full(mat)
-        if np.issubdtype(mat.dtype, np.complexfloating) and select_complex_arithmetic(
-                mat.tocsr().data, "dual" if self._complex_request == "dual" else "auto") == "full":
-            raise ValueError("this operator was not built for full complex arithmetic: make a new one for this matrix")
-        csr = mat.tocsr().astype(np.float64)
-        csr.sort_indices()
-        self.factor.refactor(csr)
-        self._read_inertia()
-        self._mat_dev = CSRMatrix(self.ctx, csr) if self._pivoted() else None
+        self._backend.refactor(mat)
 
     def solve_device_dual(self, Xr, Xi, count=None, trans=False, conjugate=False):
         """
-        complex-step operand (Xr + i Xi) <- mat^{-1} (Xr + i Xi) in place on two device blocks (see __init__).
+        complex-step operand (Xr + i Xi) <- mat^{-1} (Xr + i Xi) in place on two device blocks (see _DualBackend).
         ``trans``: mat^{-T}, i.e. x + i M^{-T}(db - dM^T x) with x = M^{-T} b; with ``conjugate`` mat^{-H}: + dM^T x.
         Full complex arithmetic: the true complex solve; in place without a copy when Xr and Xi are the two halves of
         one contiguous n x 2k block (``Z.cols(0, k)``, ``Z.cols(k, 2 k)``), else through such a block
         """
-        if self.complex_arithmetic == "full":
-            k = Xr.k
-            if (Xi.n, Xi.k) != (Xr.n, k) or Xr.n != self.shape[0]:
-                raise ValueError("shape mismatch in the complex solve")
-            with self._count_lock:
-                self.count += k if count is None else int(count)
-            halves = Xr.buf is Xi.buf and Xr.ld == Xi.ld == 2 * k and Xi.offset == Xr.offset + k
-            if halves:
-                Z = DeviceBlock(Xr.ctx, Xr.n, 2 * k, Xr.buf, Xr.offset, 2 * k)
-            else:
-                Z = Xr.ctx.empty(Xr.n, 2 * k)
-                Z.cols(0, k).copy_from(Xr)
-                Z.cols(k, 2 * k).copy_from(Xi)
-            self._solve_full(Z, trans=trans, conjugate=conjugate)
-            if not halves:
-                Xr.copy_from(Z.cols(0, k))
-                Xi.copy_from(Z.cols(k, 2 * k))
-            return Xr, Xi
-        if self._imag_dev is None:
-            raise TypeError("solve_device_dual needs an operator built on a complex (complex-step) matrix")
-        self.solve_device(Xr, count=count, trans=trans)
-        T = (self._imag_dev.transposed() if trans else self._imag_dev).apply(Xr)
-        Xi.assign_lincomb([(1.0, Xi), (1.0 if conjugate else -1.0, T)])
-        self.solve_device(Xi, count=0, trans=trans)
+        self._backend.solve_complex(Xr, Xi, trans, conjugate, lambda: self._counted(Xr.k, count))
         return Xr, Xi
 
     # -- host path (reference call surface) ------------------------------------
     def _apply_host(self, x, adjoint):
         x = np.asarray(x)
-        if self.complex_arithmetic == "full":
-            Z = self.ctx.from_host(complex_split(x.reshape(self.shape[0], -1)))
-            k = Z.k // 2
-            self.solve_device_dual(Z.cols(0, k), Z.cols(k, 2 * k), trans=adjoint, conjugate=adjoint)
-            out = complex_join(Z.get())
-            return out[:, 0] if x.ndim == 1 else out
-        if self._imag_dev is not None:
-            xc = x.astype(np.complex128).reshape(self.shape[0], -1)
-            Xr, Xi = self.ctx.from_host(np.ascontiguousarray(xc.real)), self.ctx.from_host(np.ascontiguousarray(xc.imag))
-            self.solve_device_dual(Xr, Xi, trans=adjoint, conjugate=adjoint)
-            out = Xr.get() + 1j * Xi.get()
-            return out[:, 0] if x.ndim == 1 else out
-        X = self.ctx.from_host(x.astype(np.float64).reshape(self.shape[0], -1))
-        self.solve_device(X, trans=adjoint)
-        out = X.get()
+        out = self._backend.apply_host(self, x.reshape(self.shape[0], -1), adjoint)
         return out[:, 0] if x.ndim == 1 else out
 
     def _matvec(self, x):

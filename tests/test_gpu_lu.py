@@ -358,7 +358,7 @@ def test_end_to_end_adjoint_on_golden(name, solver):
         sigma = float(g[p + "sigma"])
         A, B, mat, mode, rhs, ref, rtol = K, M, K - sigma * M, "normal", "Phib", p + "sibk_psi", 1e-12
     factor = eg.SpLuOperator(mat.tocsc(), symmetric=False)
-    assert factor.kind == "lu" and factor._pivoted()   # (adjoint._short_recurrence_applies: False)
+    assert factor.kind == "lu" and factor.refined   # (adjoint._short_recurrence_applies: False)
     if solver == "IRAM":
         s = eg.IRAM(N=6, m=60 if mode == "buckling" else 40, mode=mode)
     else:
