@@ -202,26 +202,14 @@ def test_compensated_column_dots_are_exact_to_rounding(ctx, n, k):
     """
     import math
 
+    from krylov_reference import two_prod_terms          # Veltkamp / Dekker: x*y = p + e exactly, in pure Python floats
+
     rng = np.random.default_rng(3 * n + k)
     X, Y = rng.normal(size=(n, k)), rng.normal(size=(n, k))
     if n > 2:
         X[0], Y[0] = 1e10, 1.0 + rng.uniform(size=k)
         X[n // 2], Y[n // 2] = -1e10, Y[0]                       # cancels row 0 exactly in exact arithmetic
     hi, lo = ctx.from_host(X).coldot_dd(ctx.from_host(Y))
-
-    def two_prod_terms(x, y):
-        # Veltkamp / Dekker: x*y = p + e exactly, in pure Python floats
-        out = []
-        for a, b in zip(x.tolist(), y.tolist()):
-            p = a * b
-            sa = a * 134217729.0
-            ah = sa - (sa - a)
-            al = a - ah
-            sb = b * 134217729.0
-            bh = sb - (sb - b)
-            bl = b - bh
-            out += [p, ((ah * bh - p) + ah * bl + al * bh) + al * bl]
-        return out
 
     for c in range(k):
         exact = math.fsum(two_prod_terms(X[:, c], Y[:, c]))
