@@ -649,6 +649,62 @@ def _active_range(done):
     return int(live[0]), int(live[-1]) + 1
 
 
+class _Modes:
+    """
+    Where the k modes of a lock-step round stand: ``hist[c]`` the residual norms of mode c so far (the caller's lists,
+    appended to), ``info[c]`` the step at which it met the tolerance, ``converged[c]`` whether it did, ``done[c]`` whether
+    it has stopped moving (converged, or kept as the best iterate by the solver's own rule at its step limit).
+    The test is the reference's (1223-1225 at the start, 1275 in the loops): res < rtol * rnorm0 or res < atol.
+    """
+
+    def __init__(self, hist, rtol_abs, atol):
+        self.k, self.hist = len(hist), hist
+        self.rtol_abs, self.atol = rtol_abs, atol         # (rtol_abs = rtol * rnorm0)
+        self.tol = max(rtol_abs, atol)                    # res < tol is the same test in one comparison
+        self.info = [None] * self.k
+        self.done = np.zeros(self.k, dtype=bool)
+        self.converged = np.zeros(self.k, dtype=bool)
+
+    def start(self, beta0, met=None):
+        """the start residuals of all modes; True if nothing is left to do.  ``met``: see judge"""
+        for c in range(self.k):
+            self.judge(c, 0, beta0[c], None if met is None else met[c])
+        return bool(self.done.all())
+
+    def judge(self, c, step, res, met=None):
+        """
+        mode c has residual norm ``res`` after ``step`` steps: into the history; True if that finishes the mode.
+        ``met``: the verdict, where the caller has to make the comparison in another form (the short recurrence compares
+        the squares, as the device does when it freezes a column).
+        """
+        self.hist[c].append(res)
+        if (res < self.rtol_abs or res < self.atol) if met is None else met:
+            self.info[c] = step
+            self.done[c] = self.converged[c] = True
+            return True
+        return False
+
+
+def _by_column_chunks(run, ctx, R, width):
+    """
+    ``run(a, b, block)`` -> (update, converged, info, ok) on the columns [a, b) of R, ``width`` columns at a time, stitched
+    together; stops behind the first chunk that is not ok.  A block that fits is handed through as it is, and so is what
+    ``run`` makes of it (no copy into a block of the same size).
+    """
+    k = R.k
+    if k <= width:
+        return run(0, k, R)
+    upd = ctx.zeros(R.n, k)
+    conv, info, ok = np.zeros(k, dtype=bool), [None] * k, True
+    for a in range(0, k, width):
+        b = min(k, a + width)
+        ua, conv[a:b], info[a:b], ok = run(a, b, R.cols(a, b))
+        upd.cols(a, b).copy_from(ua)
+        if not ok:
+            break
+    return upd, conv, info, ok
+
+
 def _sibk_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
     """
     One attempt of the bs_target=1 solver for all columns of R0 at once.
@@ -662,17 +718,11 @@ def _sibk_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
     k = R0.k
     Kop = prob.opB if mode == "normal" else prob.opA  # Krylov operator P K factor (ref 1249-1252)
     sgn = 1.0 if mode == "normal" else -1.0            # ref 1265-1268
-    info = [None] * k
-    done = np.zeros(k, dtype=bool)
-    converged = np.zeros(k, dtype=bool)
-    beta0 = R0.colnorms()
-    for c in range(k):
-        hist[c].append(beta0[c])
-        if beta0[c] < rtol * rnorm0 or beta0[c] < atol:  # ref 1223-1225
-            info[c] = 0
-            done[c] = converged[c] = True
+    modes = _Modes(hist, rtol * rnorm0, atol)
+    info, done, converged = modes.info, modes.done, modes.converged
+    finished = modes.start(R0.colnorms())                # ref 1223-1225
     dpsi = ctx.zeros(prob.n, k)
-    if done.all():
+    if finished:
         return dpsi, converged, info
     W = ctx.workspace_stack("krylov_W", maxiter + 1, prob.n, k)
     Z = ctx.workspace_stack("krylov_Z", maxiter, prob.n, k)  # columns of finished modes are never written: their
@@ -709,11 +759,8 @@ def _sibk_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
             rvec = np.zeros(j + 1)
             rvec[0] = r00[c]
             y, res = solve_shifted_lstsq(sgn * (lam_c[c] - sigma), H[c, : j + 1, :j], rvec)  # ref 1262-1270
-            hist[c].append(res)
-            if res < rtol * rnorm0 or res < atol:        # ref 1275
-                info[c] = j
+            if modes.judge(c, j, res):                   # ref 1275
                 Ycoef[:j, c] = y
-                done[c] = converged[c] = True
             elif j == maxiter:                           # ref 1312-1313: keep the best iterate
                 Ycoef[:j, c] = y
                 done[c] = True
@@ -748,9 +795,8 @@ def _sibk_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
         small_solves(j, cur[0], cur[1], h, hn)
         if done.all():
             break
-        if nxt is not None and prob.fac.native:          # count the sweep in flight for the modes that go on
-            with prob.fac.factor._count_lock:
-                prob.fac.factor.count += int(np.count_nonzero(~done))
+        if nxt is not None:                              # count the sweep in flight for the modes that go on
+            prob.fac.count_applications(np.count_nonzero(~done))
         if nxt is not None:
             # the step in flight keeps the range it was launched with; narrower ranges apply from the step after.
             # Columns that finished meanwhile are zeroed when the next basis vector is formed (scale above).
@@ -822,17 +868,11 @@ def _sibk_round_pair(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
     n, k = prob.n, R0.k
     Kop = prob.opB if mode == "normal" else prob.opA
     sgn = 1.0 if mode == "normal" else -1.0
-    info = [None] * k
-    done = np.zeros(k, dtype=bool)
-    converged = np.zeros(k, dtype=bool)
-    beta0 = R0.colnorms()
-    for c in range(k):
-        hist[c].append(beta0[c])
-        if beta0[c] < rtol * rnorm0 or beta0[c] < atol:  # ref 1223-1225
-            info[c] = 0
-            done[c] = converged[c] = True
+    modes = _Modes(hist, rtol * rnorm0, atol)
+    info, done, converged = modes.info, modes.done, modes.converged
+    finished = modes.start(R0.colnorms())                # ref 1223-1225
     dpsi = ctx.zeros(n, k)
-    if done.all():
+    if finished:
         return dpsi, converged, info, True
     W = ctx.workspace_stack("krylov_W2", maxiter + 2, n, k)
     Z = ctx.workspace_stack("krylov_Z2", maxiter + 1, n, k)
@@ -913,11 +953,8 @@ def _sibk_round_pair(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
                 rvec = np.zeros(jj + 1)
                 rvec[0] = r00[c]
                 y, res = solve_shifted_lstsq(sgn * (lam_c[c] - sigma), Hc[: jj + 1, :jj], rvec)  # ref 1262-1270
-                hist[c].append(res)
-                if res < rtol * rnorm0 or res < atol:    # ref 1275
-                    info[c] = jj
+                if modes.judge(c, jj, res):              # ref 1275
                     Ycoef[:jj, c] = Czc[:jj, :jj] @ y
-                    done[c] = converged[c] = True
                     break
                 if jj == maxiter or (jj == steps[-1] and len(steps) == 1):   # ref 1312-1313: keep the best iterate
                     Ycoef[:jj, c] = Czc[:jj, :jj] @ y
@@ -953,12 +990,11 @@ def _sibk_round_pair(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
         if ranges:
             nxt = (j,) + tuple(ranges[0])                 # another range waits at this cycle index
         elif more:
-            tol_c = max(rtol * rnorm0, atol)
             in_cycle = np.zeros(k, dtype=bool)
             in_cycle[lo:hi] = True                        # (their steps j+1, j+2 are the ones being solved)
             if tuning.predict_finish and j > 0:
-                stay_lax = ~done & ~_expected_to_finish(hist, done, in_cycle, tol_c, 4.0)
-                stay = ~done & ~_expected_to_finish(hist, done, in_cycle, tol_c, 0.5)
+                stay_lax = ~done & ~_expected_to_finish(hist, done, in_cycle, modes.tol, 4.0)
+                stay = ~done & ~_expected_to_finish(hist, done, in_cycle, modes.tol, 0.5)
             else:
                 stay_lax = stay = ~done
             if stay_lax.any():
@@ -988,9 +1024,9 @@ def _sibk_round_pair(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxiter, hist):
                     LAST_ROUND["cycles_repeated_for_missed_modes"] = LAST_ROUND.get("cycles_repeated_for_missed_modes", 0) + 1
                     ranges.append((int(missed[0]), int(missed[-1]) + 1))
         j += 2
-    if prob.fac.native and ok:                            # one factor application per Krylov step and mode (ref 1248);
-        with prob.fac.factor._count_lock:                 # an abandoned attempt is counted by the one-step form that redoes it
-            prob.fac.factor.count += int(sum((i if i is not None else maxiter) for i in info))
+    if ok:                                                # one factor application per Krylov step and mode (ref 1248);
+        prob.fac.count_applications(sum((i if i is not None else maxiter) for i in info))   # an abandoned attempt is
+                                                          # counted by the one-step form that redoes it
     fin = np.flatnonzero(done)
     if len(fin) and jlast > 0:
         upd = ctx.zeros(n, k)
@@ -1046,6 +1082,91 @@ def _cg_solution_coefficients(log, k):
     return S
 
 
+def _cg_projection_period(lam_c, lam_defl, sigma):
+    """
+    How often the short recurrence projects its residual (1257): every p-th step.  What the sweep's rounding (1e-13 of the
+    residual) leaves along a deflated direction B phi_j with lam_j below lam_i -- where C_i is NEGATIVE,
+    1 - (lam_i - sigma) / (lam_j - sigma) -- is multiplied by rho (1 - gam mu) per step while the residual shrinks: measured
+    on the 1 M-dof column (tools/contamination_probe.py) a factor of 30 per step relative to the residual, 4 g with g the
+    largest |mu| is the model.  Left alone it takes the recurrence apart (<r, C r>_F turns negative: step 24 on that
+    column).  p = the largest period with 1e-13 (4 g)^p < 1e-7 (measured at the ends of such periods: 3e-6 at most; the
+    recurrence's scalars feel the square of it), four at most, one if g is not finite (a deflated eigenvalue at the
+    shift); ``tuning.cg_projection_period`` overrides it.
+    """
+    if tuning.cg_projection_period:
+        return int(tuning.cg_projection_period)
+    lam_c, lam_defl = np.asarray(lam_c, dtype=float), np.asarray(lam_defl, dtype=float)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.nanmax(np.abs(1.0 - (lam_c[:, None] - sigma) / (lam_defl[None, :] - sigma)))
+    if not np.isfinite(g):
+        return 1
+    return int(max(1, min(4, np.floor(np.log(1e6) / np.log(max(4.0 * g, 1.0 + 1e-12))))))
+
+
+def _cg_frozen(h):
+    """a residual history that has stopped moving: a column that broke down (gam = 0: flag 2 on the device)"""
+    return len(h) >= 3 and h[-1] > 0.0 and abs(h[-1] - h[-2]) <= 1e-14 * h[-1] and abs(h[-2] - h[-3]) <= 1e-14 * h[-2]
+
+
+def _cg_not_converging(h):
+    """a residual that has not halved over its last ten steps: the recurrence has lost its footing (the caller's Phi is
+    not invariant enough for the deflated operator to stay positive definite in finite precision, or lam is not the
+    eigenvalue of its column)"""
+    return len(h) > 12 and not h[-1] < 0.5 * h[-11]
+
+
+def _cg_exit_report(st, k, nsteps, stalled, failed, hist, converged, tol):
+    """why the Arnoldi form takes over (LAST_ROUND["cg_exit"], for the caller's log); ``st``: the device's state rows"""
+    broke = [int(c) for c in np.flatnonzero(st[_CG_ROWS["flag"], :k] == 2.0)]
+    return {"steps": nsteps, "broke_down": broke, "stalled": stalled, "no_memory_at_step": failed[:1],
+            "breakdown_saw": {c: (float(st[10, c]), float(st[11, c]), int(st[12, c])) for c in broke} if st.shape[0] > 12 else {},
+            "residual_over_tolerance": {int(c): float(hist[c][-1] / tol) for c in range(k) if not converged[c]}}
+
+
+class _ZHistory:
+    """
+    The z = factor(r) of the steps of a short-recurrence round on an n x k block, which the solution is formed from at
+    the end: workspace stacks of _CG_CHUNK slabs each, tagged ("cg_z", allocation number, n, k), allocated as the steps
+    come and kept between calls -- for the two most recently used block shapes; a caller that walks through many widths
+    lets the others go here (``ctx.z_history_shapes``).
+    """
+
+    def __init__(self, ctx, n, k):
+        self.ctx, self.shape, self.chunks = ctx, (n, k), []
+        shapes = ctx.z_history_shapes
+        if self.shape in shapes:
+            shapes.remove(self.shape)
+        shapes.append(self.shape)
+        for old in shapes[:-2]:
+            self._drop(old)
+        del shapes[:-2]
+
+    def _drop(self, shape):
+        self.ctx.drop_workspaces(lambda t: isinstance(t, tuple) and t[0] == "cg_z" and t[2:] == shape)
+
+    def slab(self, j):
+        """the slab step j's sweep writes; EigdHipError if there is no memory for the chunk it lies in"""
+        q, i = divmod(j - 1, _CG_CHUNK)
+        while len(self.chunks) <= q:
+            self.chunks.append(self.ctx.workspace_stack(("cg_z", len(self.chunks)) + self.shape, _CG_CHUNK, *self.shape))
+        return self.chunks[q][i]
+
+    def combine_into(self, psi, Sd, nlog):
+        """psi += sum_j Sd[j] z_j over the first nlog steps (coefficients on the device)"""
+        from ._ffi import call
+
+        n, k = self.shape
+        for q, chunk in enumerate(self.chunks):
+            a, b = q * _CG_CHUNK, min(nlog, (q + 1) * _CG_CHUNK)
+            if a < b:
+                call("eigd_stack_axpy_dev", self.ctx.h, n, k, b - a, chunk.ptr, chunk.slab, chunk.k, Sd.rows(a, b).ptr, psi.ptr, psi.ld, 1.0)
+
+    def discard(self):
+        """behind a failed attempt: its stacks go before the Arnoldi form allocates its own (16 slabs of n x k per chunk)"""
+        self.chunks.clear()
+        self._drop(self.shape)
+
+
 def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, host_work=None):
     """
     All columns of R0 (at most 64) by conjugate gradients in the factor inner product, in lock step.  Same Krylov spaces
@@ -1067,85 +1188,45 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
     Kop = prob.opB if mode == "normal" else prob.opA      # Krylov operator P K factor (ref 1249-1252)
     sgn = 1.0 if mode == "normal" else -1.0                # ref 1265-1268
     nrows = int(_ffi.lib().eigd_cg_state_rows())
-    tol = max(rtol * rnorm0, atol)
+    modes = _Modes(hist, rtol * rnorm0, atol)
+    info, done, converged = modes.info, modes.done, modes.converged
+    tol = modes.tol
     tol2 = tol * tol
-    info = [None] * k
-    done = np.zeros(k, dtype=bool)
-    converged = np.zeros(k, dtype=bool)
     beta0 = R0.coldot(R0)
-    for c in range(k):
-        hist[c].append(float(np.sqrt(beta0[c])))
-        if beta0[c] < tol2:                                # ref 1223-1225
-            info[c] = 0
-            done[c] = converged[c] = True
+    finished = modes.start(np.sqrt(beta0).tolist(), met=beta0 < tol2)   # ref 1223-1225
     psi = ctx.zeros(n, k)
-    if done.all():
+    if finished:
         return psi, converged, info, True
     st_h = np.zeros((nrows, 64))
     st_h[_CG_ROWS["done"], :k] = done
     st_h[_CG_ROWS["tol2"], :k] = tol2
     st_h[_CG_ROWS["alpha"], :k] = sgn * (np.asarray(lam_c, dtype=float) - sigma)   # ref 1264-1269
     state = ctx.from_host(st_h)
-    r = R0                                                 # (the caller's block is the work block: it is consumed)
-    r_old, y = ctx.empty(n, k), ctx.empty(n, k)
+    res = [R0, ctx.empty(n, k)]                            # the residual of the last step (the caller's block is the work block:
+    y = ctx.empty(n, k)                                    # it is consumed) and of the one before, swapped by every step
     deferred = bool(tuning.cg_solution_from_history)
     if deferred:
-        psi_old = z = None
-        zchunks = []                                       # stacks of _CG_CHUNK slabs each, kept between calls
+        sol = [psi, None]
         log = ctx.zeros(2 * (maxsteps + 2), 64)            # (gam, rho) of every step, written by eigd_cg_coefficients
+        z, zhist = None, _ZHistory(ctx, n, k)
     else:
-        psi_old, z = ctx.zeros(n, k), ctx.empty(n, k)
+        sol = [psi, ctx.zeros(n, k)]                       # the iterate and the one before, swapped like the residuals
+        z, zhist = ctx.empty(n, k), None
         log = None
     failed = []                                            # (no memory for another chunk of the history)
     gave_up = []                                           # columns seen frozen or stalled while the loop ran
     # what the measured projection lets pass: a component along B Phi_D of relative size 1e-11 grows by |1 - alpha theta_j|
     # per step until it is taken out again; psi carries it at that relative size at most, and is projected once at the end
     proj_tol = tuning.cg_projection_tol
-    # How often the residual is projected at all (1257).  What the sweep's rounding (1e-13 of the residual) leaves along
-    # a deflated direction B phi_j with lam_j below lam_i -- where C_i is NEGATIVE, 1 - (lam_i - sigma) / (lam_j - sigma) --
-    # is multiplied by rho (1 - gam mu) per step while the residual shrinks: measured on the 1 M-dof column
-    # (tools/contamination_probe.py) a factor of 30 per step relative to the residual, 4 g with g the largest |mu| is the
-    # model.  Left alone it takes the recurrence apart (<r, C r>_F turns negative: step 24 on that column).  Every p-th
-    # step therefore projects the residual AND the previous one, which the three-term recurrence brings back in the next
-    # step (projecting r alone only divided the component by |1 - rho|: it kept growing from period to period);
-    # p = the largest period with 1e-13 (4 g)^p < 1e-7 (measured at the ends of such periods: 3e-6 at most; the
-    # recurrence's scalars feel the square of it), four at most.  The steps in between take their residual norms
-    # from the update kernel.
-    lam_all = np.asarray(lam_c, dtype=float)
-    lam_defl = lam_all if prob.lam_phi is None else np.asarray(prob.lam_phi, dtype=float)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        g = np.nanmax(np.abs(1.0 - (lam_all[:, None] - sigma) / (lam_defl[None, :] - sigma)))
-    proj_every = 1
-    if np.isfinite(g):
-        proj_every = int(max(1, min(4, np.floor(np.log(1e6) / np.log(max(4.0 * g, 1.0 + 1e-12))))))
-    if tuning.cg_projection_period:
-        proj_every = int(tuning.cg_projection_period)
+    # Every proj_every-th step projects the residual AND the previous one, which the three-term recurrence brings back in
+    # the next step (projecting r alone only divided the component by |1 - rho|: it kept growing from period to period).
+    # The steps in between take their residual norms from the update kernel.
+    proj_every = _cg_projection_period(lam_c, lam_c if prob.lam_phi is None else prob.lam_phi, sigma)
     LAST_ROUND["cg_projection_period"] = proj_every
     LAST_ROUND["cg_solution"] = "from the z history" if deferred else "recurrence"
 
     def sptr(lo):
         return state.cols(lo, 64).ptr
-
-    def zslab(j):
-        """the block step j's sweep writes: a slab of the history (deferred solution) or the one work block"""
-        if not deferred:
-            return z
-        q, i = divmod(j - 1, _CG_CHUNK)
-        while len(zchunks) <= q:
-            zchunks.append(ctx.workspace_stack(("cg_z", len(zchunks), n, k), _CG_CHUNK, n, k))
-        return zchunks[q][i]
-
-    if deferred:
-        # the history stacks are kept between calls per block shape; a caller that walks through many widths keeps the two
-        # last ones only (16 slabs of n x k each per allocation)
-        shapes = ctx.__dict__.setdefault("_cg_z_shapes", [])
-        if (n, k) in shapes:
-            shapes.remove((n, k))
-        shapes.append((n, k))
-        for old in shapes[:-2]:
-            for tag in [t for t in ctx.__dict__.get("_ws", {}) if isinstance(t, tuple) and t[0] == "cg_z" and t[2:] == old]:
-                del ctx.__dict__["_ws"][tag]
-        del shapes[:-2]
 
     norms_of = {}                                          # step -> device block of its residual norms (unprojected steps)
 
@@ -1153,16 +1234,15 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
         return j % proj_every == 0 or j >= maxsteps
 
     def first_part(j, lo, hi, n2, n2_lo):
-        """sweep of the residual of step j - 1 (into the history slab of step j), product with the step's inner products,
-        coefficients, recurrence of the residual (no synchronisation)"""
-        nonlocal r, r_old, psi, psi_old
+        """sweep of the residual of step j - 1 (into the history slab of step j, or the one work block), product with the
+        step's inner products, coefficients, recurrence of the residual (no synchronisation)"""
         kk = hi - lo
         try:
-            zj = zslab(j)
+            zj = zhist.slab(j) if deferred else z
         except _ffi.EigdHipError:
             failed.append(j)
             return
-        rv, zv, yv = r.cols(lo, hi), zj.cols(lo, hi), y.cols(lo, hi)
+        rv, zv, yv = res[0].cols(lo, hi), zj.cols(lo, hi), y.cols(lo, hi)
         prob.fac.apply_to(rv, zv, count=0)                # ref 1248
         n2p = None if n2 is None else n2.cols(lo - n2_lo, hi - n2_lo).ptr
         logp = log.cols(lo, 64).ptr if deferred else None
@@ -1174,18 +1254,18 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
             Kop.apply(zv, yv)                             # ref 1250 / 1252
             call("eigd_cg_coefficients", ctx.h, n, kk, zv.ptr, zv.ld, rv.ptr, rv.ld, yv.ptr, yv.ld, n2p, sptr(lo), int(j),
                  1 if j == 1 else 0, logp)
-        rov = r_old.cols(lo, hi)
+        rov = res[1].cols(lo, hi)
         own = None if project_in(j) else ctx.empty(1, kk)  # (a step that is not projected forms its own residual norms)
         if deferred:
             call("eigd_cg_update", ctx.h, n, kk, rv.ptr, rv.ld, rov.ptr, rov.ld, None, 0, None, 0, None, 0,
                  yv.ptr, yv.ld, sptr(lo), 1 if j == 1 else 0, own.ptr if own is not None else None)
         else:
-            psv, pov = psi.cols(lo, hi), psi_old.cols(lo, hi)
+            psv, pov = sol[0].cols(lo, hi), sol[1].cols(lo, hi)
             call("eigd_cg_update", ctx.h, n, kk, rv.ptr, rv.ld, rov.ptr, rov.ld, psv.ptr, psv.ld, pov.ptr, pov.ld, zv.ptr,
                  zv.ld, yv.ptr, yv.ld, sptr(lo), 1 if j == 1 else 0, own.ptr if own is not None else None)
-            psi, psi_old = psi_old, psi                    # (all columns of a block share the parity: the ranges lag one
+            sol.reverse()                                  # (all columns of a block share the parity: the ranges lag one
         norms_of[j] = own                                  # step behind the flags, see below)
-        r, r_old = r_old, r
+        res.reverse()
 
     lo, hi = _active_range(done)
     # (ref 1232 projects the start residual once more: the caller has just done that, 1193 -- nothing to take out)
@@ -1206,7 +1286,7 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
     while True:
         lo, hi = rng_j
         if _CG_TRACE_HOOK is not None:                     # (probes: the residual of step j before its projection)
-            _CG_TRACE_HOOK(prob, j, r.cols(lo, hi), lo, hi, project_in(j))
+            _CG_TRACE_HOOK(prob, j, res[0].cols(lo, hi), lo, hi, project_in(j))
         if project_in(j):
             # ref 1257 + the residual norm of 1275; measured update.  Against the N requested pairs only: along an extra
             # pair (lam_j above every lam_i) the eigenvalue of C_i lies in (0, 1) -- rounding there shrinks from step
@@ -1214,8 +1294,8 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
             if j > 1 and proj_every > 1 and tuning.cg_project_previous:
                 # the previous residual takes part in the next step's recurrence: what it carries along the deflated
                 # pairs would come back with it
-                prob.project_r_norm2(r_old.cols(lo, hi), tol=proj_tol, requested_only=not tuning.cg_project_extra_pairs)
-            n2 = prob.project_r_norm2(r.cols(lo, hi), tol=proj_tol, requested_only=not tuning.cg_project_extra_pairs)
+                prob.project_r_norm2(res[1].cols(lo, hi), tol=proj_tol, requested_only=not tuning.cg_project_extra_pairs)
+            n2 = prob.project_r_norm2(res[0].cols(lo, hi), tol=proj_tol, requested_only=not tuning.cg_project_extra_pairs)
         else:
             n2 = norms_of[j]                               # (formed by the update kernel of this step)
             call("eigd_colnorm2_publish", ctx.h, n2.ptr, hi - lo)
@@ -1233,22 +1313,14 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
             in_flight = True
         norms2 = ctx.fetch_colnorm2(hi - lo)
         for c in range(lo, hi):
-            if done[c]:
-                continue
-            hist[c].append(float(np.sqrt(max(norms2[c - lo], 0.0))))
-            if norms2[c - lo] < tol2:                     # ref 1275 (the comparison the device makes in eigd_cg_coefficients)
-                info[c] = j
-                done[c] = converged[c] = True
+            if not done[c]:                                # ref 1275 (the comparison the device makes in eigd_cg_coefficients)
+                modes.judge(c, j, float(np.sqrt(max(norms2[c - lo], 0.0))), met=norms2[c - lo] < tol2)
         if failed:
             break
-        # A column that broke down stops moving (gam = 0: flag 2 on the device) and never meets the tolerance; a
-        # recurrence that has lost its footing stalls.  Both are visible in the norms the host reads anyway: give up at
-        # once -- not after maxsteps sweeps and as many slabs of z history -- and let the Arnoldi form decide.
-        for c in np.flatnonzero(~done):
-            h = hist[c]
-            frozen = len(h) >= 3 and h[-1] > 0.0 and abs(h[-1] - h[-2]) <= 1e-14 * h[-1] and abs(h[-2] - h[-3]) <= 1e-14 * h[-2]
-            if frozen or (len(h) > 12 and not h[-1] < 0.5 * h[-11]):
-                gave_up.append(int(c))
+        # A column that broke down stops moving and never meets the tolerance; a recurrence that has lost its footing
+        # stalls.  Both are visible in the norms the host reads anyway: give up at once -- not after maxsteps sweeps and as
+        # many slabs of z history -- and let the Arnoldi form decide.
+        gave_up += [int(c) for c in np.flatnonzero(~done) if _cg_frozen(hist[c]) or _cg_not_converging(hist[c])]
         if gave_up:
             break
         if done.all() or j == maxsteps:
@@ -1262,42 +1334,31 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
                 break
         rng_j = nxt
         j += 1
+    psi = sol[0]
     if deferred and not failed and not gave_up:
         # psi = sum_j s_j z_j, coefficients and sum on the device, enqueued before the host looks at the flags (a solve
         # that ends in the Arnoldi form throws the block away)
         nlog = nsteps + 1
         Sd = ctx.empty(nlog, k)
         call("eigd_cg_solution_coefficients", ctx.h, k, log.ptr, nlog, Sd.ptr)
-        for q, chunk in enumerate(zchunks):
-            a, b = q * _CG_CHUNK, min(nlog, (q + 1) * _CG_CHUNK)
-            if a < b:
-                call("eigd_stack_axpy_dev", ctx.h, n, k, b - a, chunk.ptr, chunk.slab, chunk.k, Sd.rows(a, b).ptr, psi.ptr, psi.ld, 1.0)
+        zhist.combine_into(psi, Sd, nlog)
     st = state.get()
     # flag 2: r^T F r or <r, C r>_F not positive (the column stopped moving); flag 1: a step taken with rho = 1 because the
     # recurrence's denominator was not positive in finite precision -- a restart from the current iterate, counted only
     ok = not failed and not np.any(st[_CG_ROWS["flag"], :k] == 2.0) and bool(np.all(np.isfinite(st[_CG_ROWS["rr"], :k])))
     LAST_ROUND["cg_restarted_modes"] = LAST_ROUND.get("cg_restarted_modes", 0) + int(np.count_nonzero(st[_CG_ROWS["flag"], :k] == 1.0))
-    # an unfinished mode whose residual has not halved over its last ten steps: the recurrence is not converging (the
-    # caller's Phi is not invariant enough for the deflated operator to stay positive definite in finite precision, or
-    # lam is not the eigenvalue of its column): the Arnoldi form, which minimises the true residual step by step, decides
-    stalled = sorted(set(gave_up) | {c for c in range(k) if not converged[c] and len(hist[c]) > 12 and not hist[c][-1] < 0.5 * hist[c][-11]})
+    # an unfinished mode that is not converging at the end either (a frozen one only if the loop saw it): the Arnoldi
+    # form, which minimises the true residual step by step, decides
+    stalled = sorted(set(gave_up) | {c for c in range(k) if not converged[c] and _cg_not_converging(hist[c])})
     if stalled:
         ok = False
     if not ok and deferred:
-        # the z history of a failed attempt goes before the Arnoldi form allocates its own stacks (16 slabs of n x k per chunk)
-        zchunks.clear()
-        for tag in [t for t in ctx.__dict__.get("_ws", {}) if isinstance(t, tuple) and t[0] == "cg_z" and t[2:] == (n, k)]:
-            del ctx.__dict__["_ws"][tag]
-    if not ok:                                             # (why the Arnoldi form takes over: for the caller's log)
-        LAST_ROUND["cg_exit"] = {"steps": nsteps, "broke_down": [int(c) for c in np.flatnonzero(st[_CG_ROWS["flag"], :k] == 2.0)],
-                                 "stalled": stalled, "no_memory_at_step": failed[:1],
-                                 "breakdown_saw": {int(c): (float(st[10, c]), float(st[11, c]), int(st[12, c]))
-                                                   for c in np.flatnonzero(st[_CG_ROWS["flag"], :k] == 2.0)} if nrows > 12 else {},
-                                 "residual_over_tolerance": {int(c): float(hist[c][-1] / tol) for c in range(k) if not converged[c]}}
+        zhist.discard()
+    if not ok:
+        LAST_ROUND["cg_exit"] = _cg_exit_report(st, k, nsteps, stalled, failed, hist, converged, tol)
     prob.project_s(psi)                                    # what the measured projections let pass (see proj_tol)
-    if prob.fac.native and ok:                            # one factor application per step and mode (ref 1248)
-        with prob.fac.factor._count_lock:
-            prob.fac.factor.count += int(sum((i if i is not None else nsteps) for i in info))
+    if ok:                                                 # one factor application per step and mode (ref 1248)
+        prob.fac.count_applications(sum((i if i is not None else nsteps) for i in info))
     measured, applied = ctx.project_stats()
     LAST_ROUND["cg_steps"] = LAST_ROUND.get("cg_steps", 0) + nsteps
     LAST_ROUND["cg_projections"] = LAST_ROUND.get("cg_projections", 0) + measured
@@ -1307,23 +1368,10 @@ def _sibk_cg_round(prob, R0, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, h
 
 def _sibk_cg(prob, R, lam_c, sigma, rnorm0, rtol, atol, maxsteps, hist, host_work=None):
     """the short-recurrence solver over all columns of R, 64 at a time; (update, converged, info, ok)"""
-    k = R.k
-    upd = prob.ctx.zeros(prob.n, k) if k > 64 else None
-    conv, info, ok = np.zeros(k, dtype=bool), [None] * k, True
-    for a in range(0, k, 64):
-        b = min(k, a + 64)
-        ua, ca, ia, oka = _sibk_cg_round(prob, R.cols(a, b) if k > 64 else R, lam_c[a:b], sigma, rnorm0, rtol, atol, maxsteps,
-                                         hist[a:b], host_work=host_work if a == 0 else None)
-        if k > 64:
-            upd.cols(a, b).copy_from(ua)
-        else:
-            upd = ua
-        conv[a:b] = ca
-        info[a:b] = ia
-        ok = ok and oka
-        if not ok:
-            break
-    return upd, conv, info, ok
+    return _by_column_chunks(
+        lambda a, b, Rab: _sibk_cg_round(prob, Rab, lam_c[a:b], sigma, rnorm0, rtol, atol, maxsteps, hist[a:b],
+                                         host_work=host_work if a == 0 else None),
+        prob.ctx, R, 64)
 
 
 def _expected_to_finish(hist, done, in_cycle, tol, margin):
@@ -1352,6 +1400,34 @@ def _default_streams():
     return max(1, int(os.environ.get("EIGD_STREAMS", "1")))
 
 
+def _arnoldi_attempt(prob, R0, lam, sigma, rnorm0, rtol, atol, maxiter, hist, chunked):
+    """
+    One attempt of the Arnoldi form on the columns of R0: two Krylov steps per Gram-Schmidt pass where that is asked for
+    and fits, the one-step form otherwise and behind a pair form that lost orthogonality.  (update, converged, info).
+
+    The pair form orthogonalises 2 x min(k, 32) columns against up to maxiter slabs in one coefficient block of the
+    Gram-Schmidt kernels (60 KB of LDS): deeper histories (maxiter > 120 at 32 columns) take the one-step form, whose
+    Gram-Schmidt goes pass by pass beyond that depth.  A pair of blocks holds 2 x 32 columns: wider problems go chunk by
+    chunk if ``chunked`` (the sweeps take 32 columns at a time anyway, and the low modes, which finish first, share a
+    chunk) and to the one-step form if not.
+    """
+    k = R0.k
+    fits = maxiter * 2 * min(k, 32) * 8 <= 60 * 1024
+    if tuning.steps_per_pass == 2 and fits and (chunked or k <= 32):
+        keep = [list(hh) for hh in hist]
+        upd, conv, info, ok = _by_column_chunks(
+            lambda a, b, Rab: _sibk_round_pair(prob, Rab, lam[a:b], sigma, rnorm0, rtol, atol, maxiter, hist[a:b]),
+            prob.ctx, R0, 32)
+        if ok:
+            return upd, conv, info
+        for hh, h0 in zip(hist, keep):                    # (a pair lost orthogonality: the one-step form decides)
+            hh[:] = h0
+        for tag in ("krylov_W2", "krylov_Z2"):            # its stacks go before the one-step stacks are allocated
+            prob.ctx.drop_workspaces(tag)
+    LAST_ROUND["steps_per_pass"] = 1
+    return _sibk_round(prob, R0, lam, sigma, rnorm0, rtol, atol, maxiter, hist)
+
+
 def _run_groups(prob, Rc, lam_p, sigma, rnorm0, rtol, atol, maxiter, sub_hist, streams):
     """
     One attempt for the columns of Rc, optionally split into `streams` interleaved mode groups that run
@@ -1362,37 +1438,7 @@ def _run_groups(prob, Rc, lam_p, sigma, rnorm0, rtol, atol, maxiter, sub_hist, s
     k = Rc.k
     groups = max(1, min(int(streams), k))
     if groups == 1:
-        # the pair form orthogonalises 2 x min(k, 32) columns against up to maxiter slabs in one coefficient block of the
-        # Gram-Schmidt kernels (60 KB of LDS): deeper histories (maxiter > 120 at 32 columns) take the one-step form,
-        # whose Gram-Schmidt goes pass by pass beyond that depth
-        fits = maxiter * 2 * min(k, 32) * 8 <= 60 * 1024
-        if tuning.steps_per_pass == 2 and fits:
-            keep = [list(hh) for hh in sub_hist]
-            if 2 * k <= 64:
-                upd, conv, inf, ok = _sibk_round_pair(prob, Rc, lam_p, sigma, rnorm0, rtol, atol, maxiter, sub_hist)
-            else:
-                # a pair of blocks holds 2 x 32 columns: wider problems go chunk by chunk (the sweeps take 32 columns at
-                # a time anyway, and the low modes, which finish first, share a chunk)
-                upd = prob.ctx.zeros(Rc.n, k)
-                conv, inf, ok = np.zeros(k, dtype=bool), [None] * k, True
-                for a in range(0, k, 32):
-                    b = min(k, a + 32)
-                    ua, ca, ia, oka = _sibk_round_pair(prob, Rc.cols(a, b), lam_p[a:b], sigma, rnorm0, rtol, atol, maxiter,
-                                                       sub_hist[a:b])
-                    upd.cols(a, b).copy_from(ua)
-                    conv[a:b] = ca
-                    inf[a:b] = ia
-                    ok = ok and oka
-                    if not ok:
-                        break
-            if ok:
-                return upd, conv, inf
-            for hh, h0 in zip(sub_hist, keep):            # (a pair lost orthogonality: the one-step form decides)
-                hh[:] = h0
-            for tag in ("krylov_W2", "krylov_Z2"):        # its stacks go before the one-step stacks are allocated
-                prob.ctx.__dict__.get("_ws", {}).pop(tag, None)
-        LAST_ROUND["steps_per_pass"] = 1
-        return _sibk_round(prob, Rc, lam_p, sigma, rnorm0, rtol, atol, maxiter, sub_hist)
+        return _arnoldi_attempt(prob, Rc, lam_p, sigma, rnorm0, rtol, atol, maxiter, sub_hist, chunked=True)
     import threading
 
     parts = [np.arange(g, k, groups) for g in range(groups)]
@@ -1408,17 +1454,8 @@ def _run_groups(prob, Rc, lam_p, sigma, rnorm0, rtol, atol, maxiter, sub_hist, s
             pg = prob.on(ctxg)
             R0 = ctxg.empty(Rc.n, len(parts[g])).copy_from(Rg[g])
             hg = [sub_hist[c] for c in parts[g]]
-            kg = len(parts[g])
-            res = None
-            if tuning.steps_per_pass == 2 and 2 * kg <= 64 and maxiter * 2 * min(kg, 32) * 8 <= 60 * 1024:
-                keep = [list(hh) for hh in hg]
-                ug, cg, ig, okg = _sibk_round_pair(pg, R0, lam_p[parts[g]], sigma, rnorm0, rtol, atol, maxiter, hg)
-                if okg:
-                    res = (ug, cg, ig)
-                else:
-                    for hh, h0 in zip(hg, keep):
-                        hh[:] = h0
-            out[g] = res if res is not None else _sibk_round(pg, R0, lam_p[parts[g]], sigma, rnorm0, rtol, atol, maxiter, hg)
+            # (a group wider than 32 columns takes the one-step form: chunks are the single stream's so far)
+            out[g] = _arnoldi_attempt(pg, R0, lam_p[parts[g]], sigma, rnorm0, rtol, atol, maxiter, hg, chunked=False)
             ctxg.sync()
         except BaseException as exc:  # re-raised on the calling thread
             errors.append(exc)
@@ -1598,9 +1635,13 @@ def _sibk_sequential(prob, dPhib, dpsi, lam, sigma, rtol, atol, maxiter, bs_targ
     return info
 
 
-def sibk(Phib, A, B, lam, Phi, mode="normal", psi=None, sigma=None, factor=None, rtol=1e-10, atol=1e-30,
-         eig_atol=1e-5, maxiter=50, bs_target=1, update_guess=False, callback=None, nrestart=2, ctx=None):
-    n, N = _check_iter_args(Phib, A, B, lam, Phi, psi, mode)
+def _host_problem(Phib, A, B, lam, Phi, psi, mode, sigma, factor, ctx, check_lam=True):
+    """
+    What sibk, pgmres and pcpg do before they solve: arguments checked as the reference checks them, the default factor
+    (ref 783-790 / 954-961 / 1160-1167), the problem on the device with its eigenvectors, psi and Phib uploaded.
+    Returns (prob, sigma, the host psi that takes the result, psi and Phib on the device, lam as an array).
+    """
+    n, N = _check_iter_args(Phib, A, B, lam, Phi, psi, mode, check_lam=check_lam)
     ctx = _ctx_of(factor, ctx)
     if factor is None:
         factor, sigma = _default_factor(A, B, lam, sigma, mode, ctx)
@@ -1609,7 +1650,20 @@ def sibk(Phib, A, B, lam, Phi, mode="normal", psi=None, sigma=None, factor=None,
     _psi = psi if psi is not None else np.zeros((n, N), dtype=Phib.dtype)
     dpsi = ctx.from_host(_psi)
     dPhib = ctx.from_host(Phib)
-    lam = np.asarray(lam, dtype=float)
+    return prob, sigma, _psi, dpsi, dPhib, np.asarray(lam, dtype=float)
+
+
+def _host_result(prob, dpsi, _psi, lam, G, Glo, eig_atol):
+    """and behind the solve: the correction along the eigenvectors (ref 1324-1326), psi back in the caller's array"""
+    Cc, data = correction_coefficients(lam, G, eig_atol, prob.mode, Glo)
+    _apply_correction(dpsi, prob.Phi, Cc)
+    writable_result(_psi)[:] = dpsi.get()
+    return data
+
+
+def sibk(Phib, A, B, lam, Phi, mode="normal", psi=None, sigma=None, factor=None, rtol=1e-10, atol=1e-30,
+         eig_atol=1e-5, maxiter=50, bs_target=1, update_guess=False, callback=None, nrestart=2, ctx=None):
+    prob, sigma, _psi, dpsi, dPhib, lam = _host_problem(Phib, A, B, lam, Phi, psi, mode, sigma, factor, ctx)
     prob.lam_phi = lam
     G = -prob.Phi.tdot(dPhib)                            # ref 1180
     Glo = refine_repeated_entries(G, lam, prob.Phi, dPhib, eig_atol)
@@ -1618,10 +1672,7 @@ def sibk(Phib, A, B, lam, Phi, mode="normal", psi=None, sigma=None, factor=None,
     else:
         info = _sibk_sequential(prob, dPhib, dpsi, lam, sigma, rtol, atol, maxiter, bs_target, update_guess,
                                 callback, nrestart)
-    Cc, data = correction_coefficients(lam, G, eig_atol, mode, Glo)  # ref 1324-1326
-    _apply_correction(dpsi, prob.Phi, Cc)
-    writable_result(_psi)[:] = dpsi.get()
-    return _psi, data, info
+    return _psi, _host_result(prob, dpsi, _psi, lam, G, Glo, eig_atol), info
 
 
 # ---------------------------------------------------------------------------
@@ -1638,14 +1689,9 @@ def _pgmres_device(prob, dPhib, dpsi, lam_c, rtol, atol, maxiter, callback, rnor
     Gclo = refine(Gc, R) if refine is not None else None
     R.add_product(prob.BPhi, Gc, alpha=-1.0, beta=1.0)   # ref 990
     beta = R.colnorms()
-    hist = [[float(beta[c])] for c in range(k)]
-    info = [None] * k
-    done = np.zeros(k, dtype=bool)
-    for c in range(k):
-        if beta[c] < rtol * rnorm0 or beta[c] < atol:
-            info[c] = 0
-            done[c] = True
-    if not done.all():
+    modes = _Modes([[] for _ in range(k)], rtol * rnorm0, atol)
+    hist, info, done = modes.hist, modes.info, modes.done
+    if not modes.start(beta.tolist()):
         W = ctx.workspace_stack("krylov_W", maxiter + 1, prob.n, k)
         Z = ctx.workspace_stack("krylov_Z", maxiter, prob.n, k).zero()
         scale = np.where(done | (beta == 0.0), 0.0, 1.0 / np.where(beta == 0.0, 1.0, beta))
@@ -1675,11 +1721,8 @@ def _pgmres_device(prob, dPhib, dpsi, lam_c, rtol, atol, maxiter, callback, rnor
                 Hj = H[c, : j + 2, : j + 1]
                 y = np.linalg.lstsq(Hj, rhs, rcond=None)[0]
                 res = np.linalg.norm(Hj.dot(y) - rhs)
-                hist[c].append(res)
-                if res < rtol * rnorm0 or res < atol:
+                if modes.judge(c, j, res):
                     Ycoef[: j + 1, c] = y
-                    info[c] = j
-                    done[c] = True
                 elif j == maxiter - 1:
                     Ycoef[: j + 1, c] = y
                     info[c] = -1
@@ -1696,21 +1739,10 @@ def _pgmres_device(prob, dPhib, dpsi, lam_c, rtol, atol, maxiter, callback, rnor
 
 def pgmres(Phib, A, B, lam, Phi, mode="normal", psi=None, sigma=None, factor=None, rtol=1e-10, atol=1e-30,
            eig_atol=1e-5, maxiter=50, callback=None, ctx=None):
-    n, N = _check_iter_args(Phib, A, B, lam, Phi, psi, mode)
-    ctx = _ctx_of(factor, ctx)
-    if factor is None:
-        factor, sigma = _default_factor(A, B, lam, sigma, mode, ctx)
-    prob = DeviceProblem(ctx, A, B, factor, mode)
-    prob.set_phi(Phi_host=Phi)
-    _psi = psi if psi is not None else np.zeros((n, N), dtype=Phib.dtype)
-    dpsi = ctx.from_host(_psi)
-    lam = np.asarray(lam, dtype=float)
-    (G, Glo), info = _pgmres_device(prob, ctx.from_host(Phib), dpsi, lam, rtol, atol, maxiter, callback,
+    prob, sigma, _psi, dpsi, dPhib, lam = _host_problem(Phib, A, B, lam, Phi, psi, mode, sigma, factor, ctx)
+    (G, Glo), info = _pgmres_device(prob, dPhib, dpsi, lam, rtol, atol, maxiter, callback,
                                     refine=lambda Gm, R: refine_repeated_entries(Gm, lam, prob.Phi, R, eig_atol, sign=1.0))
-    Cc, data = correction_coefficients(lam, G, eig_atol, mode, Glo)
-    _apply_correction(dpsi, prob.Phi, Cc)
-    writable_result(_psi)[:] = dpsi.get()
-    return _psi, data, info
+    return _psi, _host_result(prob, dpsi, _psi, lam, G, Glo, eig_atol), info
 
 
 # ---------------------------------------------------------------------------
@@ -1768,21 +1800,10 @@ def _pcpg_device(prob, dPhib, dpsi, lam_c, rtol, atol, maxiter, reset, callback,
 
 def pcpg(Phib, A, B, lam, Phi, mode="normal", psi=None, sigma=None, factor=None, rtol=1e-10, atol=1e-30,
          eig_atol=1e-5, maxiter=100, reset=25, callback=None, ctx=None):
-    n, N = _check_iter_args(Phib, A, B, lam, Phi, psi, mode, check_lam=False)
-    ctx = _ctx_of(factor, ctx)
-    if factor is None:
-        factor, sigma = _default_factor(A, B, lam, sigma, mode, ctx)
-    prob = DeviceProblem(ctx, A, B, factor, mode)
-    prob.set_phi(Phi_host=Phi)
-    _psi = psi if psi is not None else np.zeros((n, N), dtype=Phib.dtype)
-    dpsi = ctx.from_host(_psi)
-    lam = np.asarray(lam, dtype=float)
-    (G, Glo), info = _pcpg_device(prob, ctx.from_host(Phib), dpsi, lam, rtol, atol, maxiter, reset, callback,
+    prob, sigma, _psi, dpsi, dPhib, lam = _host_problem(Phib, A, B, lam, Phi, psi, mode, sigma, factor, ctx, check_lam=False)
+    (G, Glo), info = _pcpg_device(prob, dPhib, dpsi, lam, rtol, atol, maxiter, reset, callback,
                                   refine=lambda Gm, R: refine_repeated_entries(Gm, lam, prob.Phi, R, eig_atol, sign=1.0))
-    Cc, data = correction_coefficients(lam, G, eig_atol, mode, Glo)
-    _apply_correction(dpsi, prob.Phi, Cc)
-    writable_result(_psi)[:] = dpsi.get()
-    return _psi, data, info
+    return _psi, _host_result(prob, dpsi, _psi, lam, G, Glo, eig_atol), info
 
 
 # ---------------------------------------------------------------------------

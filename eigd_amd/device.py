@@ -28,6 +28,9 @@ class Context:
         self.h = h
         self.device = int(device)
         self.parent = _parent
+        # (n, k) of the block shapes whose short-recurrence z histories sit among the workspaces, least recently used
+        # first: kept here because it has to outlive a solve; read and written by adjoint._ZHistory alone
+        self.z_history_shapes = []
 
     def fork(self, index=0):
         """child context number `index` on the same device (own stream); created once and kept"""
@@ -152,8 +155,19 @@ class Context:
             cache[tag] = st
         return st
 
+    def workspace_tags(self):
+        """the tags of the workspace stacks held at the moment"""
+        return list(self.__dict__.get("_ws", {}))
+
+    def drop_workspaces(self, match):
+        """let go of the stacks whose tag equals ``match`` or, ``match`` being a function of the tag, satisfies it"""
+        cache = self.__dict__.get("_ws", {})
+        hit = match if callable(match) else (lambda tag: tag == match)
+        for tag in [t for t in cache if hit(t)]:
+            del cache[tag]
+
     def release_workspaces(self):
-        self.__dict__.pop("_ws", None)
+        self.drop_workspaces(lambda tag: True)
         self.trim_pool()
 
     def trim_pool(self):

@@ -578,3 +578,9 @@ class FactorApply:
         Xout.set(alpha * out.reshape(Xin.n, Xin.k))
         return Xout
 
+    def count_applications(self, n):
+        """``n`` applications per mode that were enqueued with ``count=0`` (the lock-step loops learn only afterwards how
+        many modes a sweep served) go into the native factor's counter; a foreign factor keeps its own count"""
+        if self.native:
+            self.factor._counted(0, n)
+

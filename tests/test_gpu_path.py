@@ -989,6 +989,35 @@ def test_concurrent_mode_groups_on_streams_match_single_stream(monkeypatch):
     assert np.allclose(hist3, hist1, rtol=1e-6, atol=1e-14)
 
 
+def test_mode_groups_on_streams_climb_down_the_attempt_ladder_like_the_single_stream(monkeypatch):
+    """every pair of the two-step form rejected (pair_defect_tol < 0): each group thread puts its histories back and redoes
+    its columns in the one-step form, as the single stream does; same psi, info, counts and histories"""
+    import eigd_amd as eg
+    from eigd_amd import adjoint as adj
+
+    monkeypatch.setattr(eg.tuning, "recurrence", "arnoldi")
+    monkeypatch.setattr(eg.tuning, "steps_per_pass", 2)
+    monkeypatch.setattr(eg.tuning, "pair_defect_tol", -1.0)
+
+    g = load_golden("g4_laplace900_basiclanczos")
+    K, M = csr_from(g, "K"), csr_from(g, "M")
+    fac = eg.SpLuOperator((K + 0.1 * M).tocsc())
+    s = eg.BasicLanczos(N=6, m=60)
+    s.solve(K, M, fac, -0.1)
+    out = {}
+    for streams in (1, 3):
+        hist = []
+        fac.count = 0
+        adj.LAST_ROUND["steps_per_pass"] = None
+        psi, _ = s.solve_adjoint(g["Phib"], method="sibk", rtol=1e-12, callback=hist.append, streams=streams)
+        assert adj.LAST_ROUND["steps_per_pass"] == 1
+        out[streams] = (psi, list(s.last_info), hist, fac.count)
+    (psi1, info1, hist1, c1), (psi3, info3, hist3, c3) = out[1], out[3]
+    assert info3 == info1 and c3 == c1
+    assert len(hist3) == len(hist1) and np.allclose(hist3, hist1, rtol=1e-6, atol=1e-14)
+    assert relerr(psi3, psi1) < 1e-11
+
+
 def test_interior_shift_finds_eigenvalues_on_both_sides():
     """shift-invert around an interior shift (indefinite factor): the Ritz values nearest to sigma, residual-checked"""
     import eigd_amd as eg

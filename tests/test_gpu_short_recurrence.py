@@ -203,8 +203,41 @@ def test_history_stacks_are_kept_for_the_two_last_block_shapes_only():
     fac = eg.SpLuOperator((K + 0.1 * M).tocsc(), ctx=ctx)
     for N in (6, 5, 4, 3):
         eg.sibk(Phib[:, :N], K, M, lam[:N], Phi[:, :N], factor=fac, sigma=-0.1, rtol=1e-10, ctx=ctx)
-    tags = [t for t in ctx.__dict__.get("_ws", {}) if isinstance(t, tuple) and t[0] == "cg_z"]
+    tags = [t for t in ctx.workspace_tags() if isinstance(t, tuple) and t[0] == "cg_z"]
     assert sorted({t[3] for t in tags}) == [3, 4], tags
+
+
+def test_context_hands_out_its_workspace_tags_and_drops_workspaces_by_tag():
+    """Context.workspace_tags / drop_workspaces, which the z history is kept and let go through: the stacks of the two
+    last block shapes are held, dropping them by predicate leaves none, and the next solve allocates them again and
+    returns the same psi bit for bit"""
+    import eigd_amd as eg
+    from eigd_amd import adjoint as adj
+    from eigd_amd.device import default_context
+
+    ctx = default_context()
+    g = load_golden("g4_laplace900_basiclanczos")
+    K, M = csr_from(g, "K"), csr_from(g, "M")
+    lam, Phi, Phib = g["normal_lam"], g["normal_Phi"], g["Phib"]
+    fac = eg.SpLuOperator((K + 0.1 * M).tocsc(), ctx=ctx)
+
+    def is_z(t):
+        return isinstance(t, tuple) and t[0] == "cg_z"
+
+    for N in (6, 5, 4, 3):
+        psi, _, _ = eg.sibk(Phib[:, :N], K, M, lam[:N], Phi[:, :N], factor=fac, sigma=-0.1, rtol=1e-10, ctx=ctx)
+        assert adj.LAST_ROUND["recurrence"] == "short"
+    tags = [t for t in ctx.workspace_tags() if is_z(t)]
+    assert sorted({t[3] for t in tags}) == [3, 4], tags
+    ctx.drop_workspaces(is_z)
+    assert not [t for t in ctx.workspace_tags() if is_z(t)]
+    again, _, _ = eg.sibk(Phib[:, :3], K, M, lam[:3], Phi[:, :3], factor=fac, sigma=-0.1, rtol=1e-10, ctx=ctx)
+    assert np.array_equal(again, psi)
+    assert {t[3] for t in ctx.workspace_tags() if is_z(t)} == {3}
+    first = ("cg_z", 0, K.shape[0], 3)                       # (by the tag itself: the first 16 slabs of that history)
+    assert first in ctx.workspace_tags()
+    ctx.drop_workspaces(first)
+    assert first not in ctx.workspace_tags()
 
 
 def test_solution_coefficients_on_the_device_match_the_host_twin():
@@ -286,7 +319,7 @@ def test_short_recurrence_steps_aside_where_it_does_not_apply(monkeypatch):
         from eigd_amd.device import default_context
 
         assert adj.LAST_ROUND["cg_exit"]["steps"] <= 20, adj.LAST_ROUND["cg_exit"]
-        tags = [t for t in default_context().__dict__.get("_ws", {}) if isinstance(t, tuple) and t[0] == "cg_z" and t[3] == len(sel)]
+        tags = [t for t in default_context().workspace_tags() if isinstance(t, tuple) and t[0] == "cg_z" and t[3] == len(sel)]
         assert not tags
     psi_o, data_o, info_o = orc.sibk(Phib[:, sel], K, M, lam[sel], Phi[:, sel], factor=fac_o, sigma=sigma, rtol=1e-12)
     assert relerr(psi_d, psi_o) < RTOL
