@@ -190,17 +190,11 @@ def test_coefficients_of_one_step_against_exact_dots(ctx, n, k, first):
         assert same_bits(blk.get(), inp[x])
 
 
-@pytest.mark.parametrize("first", [1, 0])
-@pytest.mark.parametrize("k", [5, 17, 32])
-def test_coefficients_out_of_the_product_pass_against_exact_dots(ctx, k, first):
-    """eigd_spmm_cg on a tiled matrix (5 <= k <= 32): y bitwise the plain product, coefficients within the bound"""
-    from eigd_amd.device import CSRMatrix
-    from test_symbolic_cpu import grid_matrix
-
-    A = grid_matrix(61, 47, 2, seed=k)
-    A = (A + A.T).tocsr()                                     # diagonally dominant: z.Az is dominated by positive terms
+def product_pass_case(A, k, first, seed=None):
+    """host side of one eigd_spmm_cg call on the matrix A (z.Az dominated by its positive terms): inputs, exact inner
+    products, the expected step and its tolerances (shared with tests/test_gpu_product_variants.py)"""
     n = A.shape[0]
-    rng = np.random.default_rng(k)
+    rng = np.random.default_rng(k if seed is None else seed)
     Rh = rng.normal(size=(n, k))
     Zh = rng.uniform(0.5, 2.0, size=(n, k)) * Rh
     Yh = A @ Zh
@@ -219,14 +213,36 @@ def test_coefficients_out_of_the_product_pass_against_exact_dots(ctx, k, first):
     tol, worst = coef_tolerances(cs, st, inp, m)
     print(f"k={k} chain {m} worst relative bound {worst:.3g}")
     assert worst < 1e-12
-    dA = CSRMatrix(ctx, A)
-    R, Z, Y = Padded(ctx, Rh), Padded(ctx, Zh), Padded(ctx, np.full((n, k), np.nan))
-    state, log = Rows64(ctx, NROWS, k, st), Rows64(ctx, 8, k)
+    return {"k": k, "first": first, "step": step, "R": Rh, "Z": Zh, "Y": Yh, "st": st, "cs": cs, "tol": tol}
+
+
+def run_product_pass(ctx, dA, case):
+    """one eigd_spmm_cg call for a product_pass_case: y bitwise the plain product, coefficients within the bound; returns
+    (y, the state block) as the device left them"""
+    k, step, first = case["k"], case["step"], case["first"]
+    n = case["R"].shape[0]
+    R, Z, Y = Padded(ctx, case["R"]), Padded(ctx, case["Z"]), Padded(ctx, np.full((n, k), np.nan))
+    state, log = Rows64(ctx, NROWS, k, case["st"]), Rows64(ctx, 8, k)
     s0, l0 = state.flat(), log.flat()
     call("eigd_spmm_cg", ctx.h, dA.h, k, Z.v.ptr, Z.v.ld, Y.v.ptr, Y.v.ld, R.v.ptr, R.v.ld, None, state.ptr, step, first,
          log.ptr)
-    assert same_bits(Y.get(), Yh)
-    check_coef(state, log, s0, state.flat(), l0, log.flat(), cs, tol, step)
+    y = Y.get()
+    assert same_bits(y, case["Y"])
+    s1 = state.flat()
+    check_coef(state, log, s0, s1, l0, log.flat(), case["cs"], case["tol"], step)
+    return y, state.block(s1)
+
+
+@pytest.mark.parametrize("first", [1, 0])
+@pytest.mark.parametrize("k", [5, 17, 32])
+def test_coefficients_out_of_the_product_pass_against_exact_dots(ctx, k, first):
+    """eigd_spmm_cg on a tiled matrix (5 <= k <= 32): y bitwise the plain product, coefficients within the bound"""
+    from eigd_amd.device import CSRMatrix
+    from test_symbolic_cpu import grid_matrix
+
+    A = grid_matrix(61, 47, 2, seed=k)
+    A = (A + A.T).tocsr()                                     # diagonally dominant: z.Az is dominated by positive terms
+    run_product_pass(ctx, CSRMatrix(ctx, A), product_pass_case(A, k, first))
 
 
 # ---- the update ---------------------------------------------------------------------------------------------------------
