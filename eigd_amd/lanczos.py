@@ -56,89 +56,6 @@ def complex_step_eigh(T):
     return lam + 1j * np.diag(D), Q + 1j * (Q @ Cf)
 
 
-class _DualLanczosDevice:
-    """
-    Lanczos basis in complex-step (dual-number) arithmetic on the device: every vector is a pair of real n-vectors
-    (value, forward derivative), every product drops the term with two derivative factors (1e-40 relative at the
-    reference's step of 1e-20, far below rounding), nothing is conjugated (reference inner product ``y.dot(B @ x)``,
-    1503).  Real kernels only: B = Br + i Bi is two CSR matrices, the factor an SpLuOperator built on a complex matrix.
-    """
-
-    def __init__(self, ctx, Br, Bi, factor, n, nvec):
-        from .operators import DeviceOperator
-
-        self.ctx, self.n, self.fac = ctx, n, factor
-        self.Br, self.Bi = DeviceOperator(ctx, Br), DeviceOperator(ctx, Bi)
-        self.Vr, self.Vi = ctx.stack(nvec, n, 1), ctx.stack(nvec, n, 1)
-        self.BVr, self.BVi = ctx.stack(nvec, n, 1), ctx.stack(nvec, n, 1)
-        self.wr, self.wi, self.t = ctx.empty(n, 1), ctx.empty(n, 1), ctx.empty(n, 1)
-
-    def apply_B(self, vr, vi, wr, wi):
-        """(wr + i wi) = (Br + i Bi)(vr + i vi)"""
-        self.Br.apply(vr, wr)
-        self.Br.apply(vi, wi)
-        self.Bi.apply(vr, self.t)
-        wi.assign_lincomb([(1.0, wi), (1.0, self.t)])
-
-    def normalize_into(self, vr, vi, j):
-        """V[j] = v / sqrt(v . B v), BV[j] = B V[j]; returns the complex norm"""
-        self.apply_B(vr, vi, self.wr, self.wi)
-        re = float(vr.coldot(self.wr)[0])
-        im = float(vr.coldot(self.wi)[0]) + float(vi.coldot(self.wr)[0])
-        br = np.sqrt(re)
-        beta = complex(br, 0.5 * im / br)
-        cr, ci = 1.0 / br, -beta.imag / (br * br)  # 1 / beta
-        self.Vr[j].assign_lincomb([(cr, vr)])
-        self.Vi[j].assign_lincomb([(cr, vi), (ci, vr)])
-        self.BVr[j].assign_lincomb([(cr, self.wr)])
-        self.BVi[j].assign_lincomb([(cr, self.wi), (ci, self.wr)])
-        return beta
-
-    def project_out(self, vr, vi, j0, ns):
-        """v <- v - V[:, j0:j0+ns] (BV^T v), twice (as the real path); returns the summed complex coefficients"""
-        tot = np.zeros(ns, dtype=complex)
-        for _ in range(2):
-            hr = self.BVr.dot(vr, ns=ns, j0=j0)
-            hi = self.BVr.dot(vi, ns=ns, j0=j0) + self.BVi.dot(vr, ns=ns, j0=j0)
-            self.Vr.axpy_into(vi, hi, alpha=-1.0, j0=j0)
-            self.Vi.axpy_into(vi, hr, alpha=-1.0, j0=j0)
-            self.Vr.axpy_into(vr, hr, alpha=-1.0, j0=j0)
-            tot += hr[:, 0] + 1j * hi[:, 0]
-        return tot
-
-    def apply_op(self, j, vr, vi):
-        """v = factor(B V[j])"""
-        vr.copy_from(self.BVr[j])
-        vi.copy_from(self.BVi[j])
-        self.fac.solve_device_dual(vr, vi)
-
-    def axpy_basis(self, vr, vi, coef, j):
-        """v += coef * V[j] for a complex scalar"""
-        vi.assign_lincomb([(1.0, vi), (coef.real, self.Vi[j]), (coef.imag, self.Vr[j])])
-        vr.assign_lincomb([(1.0, vr), (coef.real, self.Vr[j])])
-
-    def times(self, Y, m):
-        """V[:, :m] @ Y for a complex m x q matrix -> host complex array"""
-        Y = np.asarray(Y, dtype=complex)
-        q = Y.shape[1]
-        outr, outi, tmp = self.ctx.empty(self.n, q), self.ctx.empty(self.n, q), self.ctx.empty(self.n, q)
-        self.Vr.times_into(outr, np.ascontiguousarray(Y.real), ns=m)
-        self.Vr.times_into(outi, np.ascontiguousarray(Y.imag), ns=m)
-        self.Vi.times_into(tmp, np.ascontiguousarray(Y.real), ns=m)
-        outi.assign_lincomb([(1.0, outi), (1.0, tmp)])
-        return outr.get() + 1j * outi.get()
-
-    def basis_to_host(self, m):
-        from ._ffi import call, hptr
-
-        out = []
-        for st in (self.Vr, self.Vi):
-            Vt = np.empty((m, self.n))
-            call("eigd_d2h", self.ctx.h, hptr(Vt), st.ptr, 8 * self.n * m)
-            out.append(Vt.T)
-        return out[0] + 1j * out[1]
-
-
 def _check_shapes(A, B, factor):
     n = A.shape[1]
     if A.shape != (n, n):
@@ -150,8 +67,102 @@ def _check_shapes(A, B, factor):
     return n
 
 
+def reduced_problem(alpha, beta, m, sigma, mode):
+    """eigh of the leading m x m tridiagonal + sort (ref 1416-1439); a real T takes complex_step_eigh's real branch"""
+    T = np.diag(alpha[:m]) + np.diag(beta[: m - 1], 1) + np.diag(beta[: m - 1], -1)
+    theta, Y = complex_step_eigh(T)
+    lam, indices = ritz_to_eigs(theta, sigma, mode)
+    return theta, Y, T, lam, indices
+
+
+def leading_run_converged(beta_last, Yrow, N, tol):
+    """leading run of sorted Ritz pairs with |beta y_last| < tol (ref 1441-1451)"""
+    count = 0
+    for e in np.abs(beta_last * Yrow):
+        if e < tol:
+            count += 1
+        else:
+            break
+    return count >= N
+
+
+def wanted_pairs(lam, indices, m, N, Ntarget, eig_atol):
+    """N of the returned pairs (ref 1615-1625): Ntarget widened over numerically repeated Ritz values, else N with a
+    warning where the cut runs through such a pair.  Real parts are compared (the identity for real data)."""
+    def repeated(q):
+        return _is_close(lam[indices[q - 1]].real, lam[indices[q]].real, eig_atol)
+
+    if Ntarget is not None:
+        N = Ntarget
+        while N < m and repeated(N):
+            N += 1
+    elif repeated(N):
+        warnings.warn(f"BasicLanczos: Ritz values {N} and {N+1} are numerically repeated.")
+    return N
+
+
+def basic_lanczos_recurrence(basis, m_max, nchk, tol, ortho_type, sigma, mode):
+    """
+    The un-restarted shift-invert Lanczos recurrence (ref 1483-1605), host decisions only; returns (alpha, beta, m).
+    The vectors live behind ``basis``, in real arithmetic (_LanczosDevice) or in dual numbers for the reference's
+    complex-step evaluation (_DualLanczosDevice); numpy twins of both are in the CPU tests.  The basis protocol:
+
+        dtype, n               float64 or complex128 (alpha, beta and the reduced problem follow it); the problem size
+        selective_passes       Gram-Schmidt passes of selective orthogonalisation: 1 real, 2 dual
+        start(v0)              V[0] = v0 / |v0|_B
+        apply_op(j)            work = factor(B V[j])
+        subtract(coef, j)      work -= coef V[j]
+        project_out(j0, ns, passes) -> (ns,)   work -= V[:, j0:j0+ns] (BV^T work), ``passes`` times; summed coefficients
+        lock(Yc, m), unlock()  S = V[:, :m] Yc and B S, replacing any earlier S; no S
+        project_locked()       work -= S (BS^T work), selective_passes times; nothing without S
+        normalize_into(j) -> beta              V[j] = work / |work|_B, BV[j] = B V[j]
+        ritz_vectors(Y, m)     V[:, :m] Y (for the caller, after the loop)
+    """
+    alpha = np.zeros(m_max, dtype=basis.dtype)
+    beta = np.zeros(m_max, dtype=basis.dtype)
+    basis.start(np.random.default_rng(12345).uniform(size=basis.n, low=-1.0, high=1.0))  # ref 1514-1515
+    m = m_max
+    for i in range(1, m_max + 1):
+        basis.apply_op(i - 1)                                              # ref 1524
+        if i > 1:
+            basis.subtract(beta[i - 2], i - 2)                             # ref 1526
+        if ortho_type == "full":
+            alpha[i - 1] = basis.project_out(0, i, 2)[i - 1]               # ref 1529-1534
+        else:
+            j0 = max(0, i - 2)                                             # ref 1563: the two previous vectors
+            alpha[i - 1] = basis.project_out(j0, i - j0, basis.selective_passes)[-1]
+            basis.project_locked()                                         # ref 1571-1574
+        beta[i - 1] = basis.normalize_into(i)                              # ref 1537-1538
+        if i >= 2:
+            theta, Y, T, lam, indices = reduced_problem(alpha, beta, i, sigma, mode)
+            Y0 = Y[:, indices]
+            if leading_run_converged(beta[i - 1], Y0[i - 1, :], nchk, tol):
+                m = i
+                break
+            if ortho_type == "selective":                                  # ref 1596-1605
+                errs = np.abs(beta[i - 1] * Y0[i - 1, :])
+                conv = [j for j in range(i) if errs[j] < np.sqrt(tol)]
+                if conv:
+                    basis.lock(Y0[:, conv], i)
+                else:
+                    basis.unlock()
+    return alpha, beta, m
+
+
+def _stack_to_host(ctx, stack, n, m):
+    """the first m slabs of a k = 1 stack as the columns of an n x m host view"""
+    from ._ffi import call, hptr
+
+    Vt = np.empty((m, n))
+    call("eigd_d2h", ctx.h, hptr(Vt), stack.ptr, 8 * n * m)
+    return Vt.T
+
+
 class _LanczosDevice:
-    """basis storage + the B-inner-product Gram-Schmidt step shared by both solvers"""
+    """real basis of basic_lanczos_recurrence: V and B V resident as k = 1 stacks, one work vector"""
+
+    dtype = np.float64
+    selective_passes = 1
 
     def __init__(self, prob, nvec):
         self.prob = prob
@@ -160,35 +171,177 @@ class _LanczosDevice:
         self.V = self.ctx.stack(nvec, self.n, 1)
         self.BV = self.ctx.stack(nvec, self.n, 1)
         self.w = self.ctx.empty(self.n, 1)
+        self.S = self.BS = None
 
-    def normalize_into(self, v, j):
+    def start(self, v0):
+        self.v = self.ctx.from_host(v0)
+        self.normalize_into(0)
+
+    def normalize_into(self, j):
         """V[j] = v / ||v||_B, BV[j] = B v / ||v||_B ; returns the norm"""
+        v = self.v
         self.prob.opB.apply(v, self.w)
         nrm = float(np.sqrt(v.coldot(self.w)[0]))
         self.V[j].assign_lincomb([(1.0 / nrm, v)])
         self.BV[j].assign_lincomb([(1.0 / nrm, self.w)])
         return nrm
 
-    def orthogonalize(self, v, ns):
-        """v <- v - V[:, :ns] (BV[:, :ns]^T v), twice; returns the summed coefficients (ns,)"""
-        h1 = self.BV.dot(v, ns=ns)
-        self.V.axpy_into(v, h1, alpha=-1.0)
-        h2 = self.BV.dot(v, ns=ns)
-        self.V.axpy_into(v, h2, alpha=-1.0)
-        return (h1 + h2)[:, 0]
+    def apply_op(self, j):
+        self.v.copy_from(self.BV[j])
+        self.prob.fac(self.v)
 
-    def apply_op(self, j, out):
-        """out = factor(B V[j])"""
-        out.copy_from(self.BV[j])
-        self.prob.fac(out)
+    def subtract(self, coef, j):
+        self.v.assign_lincomb([(1.0, self.v), (-coef, self.V[j])])
+
+    def project_out(self, j0, ns, passes):
+        tot = None
+        for _ in range(passes):
+            h = self.BV.dot(self.v, ns=ns, j0=j0)
+            self.V.axpy_into(self.v, h, alpha=-1.0, j0=j0)
+            tot = h if tot is None else tot + h
+        return tot[:, 0]
+
+    def lock(self, Yc, m):
+        self.S = self.ritz_vectors(Yc, m)
+        self.BS = self.prob.opB.apply(self.S)
+
+    def unlock(self):
+        self.S = self.BS = None
+
+    def project_locked(self):
+        if self.S is not None:
+            hs = self.BS.tdot(self.v)
+            self.v.add_product(self.S, hs, alpha=-1.0, beta=1.0)
+
+    def ritz_vectors(self, Y, m):
+        """V[:, :m] Y as a device block"""
+        out = self.ctx.empty(self.n, Y.shape[1])
+        self.V.times_into(out, Y, ns=m)
         return out
 
     def basis_to_host(self, m):
-        from ._ffi import call, hptr
+        return np.ascontiguousarray(_stack_to_host(self.ctx, self.V, self.n, m))
 
-        Vt = np.empty((m, self.n))
-        call("eigd_d2h", self.ctx.h, hptr(Vt), self.V.ptr, 8 * self.n * m)
-        return np.ascontiguousarray(Vt.T)
+
+def _split_complex_step_B(B, factor):
+    """(Br, Bi) of a complex-step B with one sparsity pattern, after the checks of what the dual basis can run on"""
+    from scipy import sparse
+
+    if not (isinstance(factor, SpLuOperator) and factor.dual):
+        raise TypeError("the complex-step path needs an eigd_amd.SpLuOperator built on the complex shifted matrix")
+    if not sparse.issparse(B):
+        raise TypeError("the complex-step path needs B as a scipy sparse matrix")
+    Bc = sparse.csr_matrix(B).astype(np.complex128)
+    Bc.sort_indices()
+    return (sparse.csr_matrix((Bc.data.real.copy(), Bc.indices, Bc.indptr), shape=Bc.shape),
+            sparse.csr_matrix((Bc.data.imag.copy(), Bc.indices, Bc.indptr), shape=Bc.shape))
+
+
+class _DualLanczosDevice:
+    """
+    Basis of basic_lanczos_recurrence in complex-step (dual-number) arithmetic on the device: every vector is a pair of
+    real n-vectors (value, forward derivative), every product drops the term with two derivative factors (1e-40 relative
+    at the reference's step of 1e-20, far below rounding), nothing is conjugated (reference inner product
+    ``y.dot(B @ x)``, 1503).  Real kernels only: B = Br + i Bi is two CSR matrices, the factor an SpLuOperator built on a
+    complex matrix.
+    """
+
+    dtype = np.complex128
+    selective_passes = 2
+
+    def __init__(self, ctx, Br, Bi, factor, n, nvec):
+        from .operators import DeviceOperator
+
+        self.ctx, self.n, self.fac = ctx, n, factor
+        self.Br, self.Bi = DeviceOperator(ctx, Br), DeviceOperator(ctx, Bi)
+        self.Vr, self.Vi = ctx.stack(nvec, n, 1), ctx.stack(nvec, n, 1)
+        self.BVr, self.BVi = ctx.stack(nvec, n, 1), ctx.stack(nvec, n, 1)
+        self.wr, self.wi, self.t = ctx.empty(n, 1), ctx.empty(n, 1), ctx.empty(n, 1)
+        self.S = None                                      # (Sr, Si, BSr, BSi) while Ritz vectors are locked
+
+    def start(self, v0):
+        self.vr, self.vi = self.ctx.from_host(v0), self.ctx.zeros(self.n, 1)
+        self.normalize_into(0)
+
+    def apply_B(self, vr, vi, wr, wi, t):
+        """(wr + i wi) = (Br + i Bi)(vr + i vi)"""
+        self.Br.apply(vr, wr)
+        self.Br.apply(vi, wi)
+        self.Bi.apply(vr, t)
+        wi.assign_lincomb([(1.0, wi), (1.0, t)])
+
+    def normalize_into(self, j):
+        """V[j] = v / sqrt(v . B v), BV[j] = B V[j]; returns the complex norm"""
+        vr, vi = self.vr, self.vi
+        self.apply_B(vr, vi, self.wr, self.wi, self.t)
+        re = float(vr.coldot(self.wr)[0])
+        im = float(vr.coldot(self.wi)[0]) + float(vi.coldot(self.wr)[0])
+        br = np.sqrt(re)
+        beta = complex(br, 0.5 * im / br)
+        cr, ci = 1.0 / br, -beta.imag / (br * br)  # 1 / beta
+        self.Vr[j].assign_lincomb([(cr, vr)])
+        self.Vi[j].assign_lincomb([(cr, vi), (ci, vr)])
+        self.BVr[j].assign_lincomb([(cr, self.wr)])
+        self.BVi[j].assign_lincomb([(cr, self.wi), (ci, self.wr)])
+        return beta
+
+    def apply_op(self, j):
+        self.vr.copy_from(self.BVr[j])
+        self.vi.copy_from(self.BVi[j])
+        self.fac.solve_device_dual(self.vr, self.vi)
+
+    def subtract(self, coef, j):
+        vr, vi, c = self.vr, self.vi, -coef
+        vi.assign_lincomb([(1.0, vi), (c.real, self.Vi[j]), (c.imag, self.Vr[j])])
+        vr.assign_lincomb([(1.0, vr), (c.real, self.Vr[j])])
+
+    def project_out(self, j0, ns, passes):
+        vr, vi = self.vr, self.vi
+        tot = np.zeros(ns, dtype=complex)
+        for _ in range(passes):
+            hr = self.BVr.dot(vr, ns=ns, j0=j0)
+            hi = self.BVr.dot(vi, ns=ns, j0=j0) + self.BVi.dot(vr, ns=ns, j0=j0)
+            self.Vr.axpy_into(vi, hi, alpha=-1.0, j0=j0)
+            self.Vi.axpy_into(vi, hr, alpha=-1.0, j0=j0)
+            self.Vr.axpy_into(vr, hr, alpha=-1.0, j0=j0)
+            tot += hr[:, 0] + 1j * hi[:, 0]
+        return tot
+
+    def lock(self, Yc, m):
+        ctx, n, q = self.ctx, self.n, Yc.shape[1]
+        S = self.ritz_vectors(Yc, m)
+        Sr, Si = ctx.from_host(np.ascontiguousarray(S.real)), ctx.from_host(np.ascontiguousarray(S.imag))
+        BSr, BSi = ctx.empty(n, q), ctx.empty(n, q)
+        self.apply_B(Sr, Si, BSr, BSi, ctx.empty(n, q))
+        self.S = (Sr, Si, BSr, BSi)
+
+    def unlock(self):
+        self.S = None
+
+    def project_locked(self):
+        if self.S is None:
+            return
+        (Sr, Si, BSr, BSi), vr, vi = self.S, self.vr, self.vi
+        for _ in range(self.selective_passes):
+            hr = BSr.tdot(vr)
+            hi = BSr.tdot(vi) + BSi.tdot(vr)
+            vi.add_product(Sr, hi, alpha=-1.0, beta=1.0)
+            vi.add_product(Si, hr, alpha=-1.0, beta=1.0)
+            vr.add_product(Sr, hr, alpha=-1.0, beta=1.0)
+
+    def ritz_vectors(self, Y, m):
+        """V[:, :m] @ Y for a complex m x q matrix -> host complex array"""
+        Y = np.asarray(Y, dtype=complex)
+        q = Y.shape[1]
+        outr, outi, tmp = self.ctx.empty(self.n, q), self.ctx.empty(self.n, q), self.ctx.empty(self.n, q)
+        self.Vr.times_into(outr, np.ascontiguousarray(Y.real), ns=m)
+        self.Vr.times_into(outi, np.ascontiguousarray(Y.imag), ns=m)
+        self.Vi.times_into(tmp, np.ascontiguousarray(Y.real), ns=m)
+        outi.assign_lincomb([(1.0, outi), (1.0, tmp)])
+        return outr.get() + 1j * outi.get()
+
+    def basis_to_host(self, m):
+        return _stack_to_host(self.ctx, self.Vr, self.n, m) + 1j * _stack_to_host(self.ctx, self.Vi, self.n, m)
 
 
 def _svqb(gram):
@@ -570,8 +723,20 @@ class _BlockLanczosDevice:
 class _AdjointAPI:
     """solve_adjoint / eval_adjoint_residual_norm / add_total_derivative (ref 1652-1870, 1988-2207)"""
 
-    # subclasses provide: _lamN(), _warn_dl(), self._dev (LanczosDevice), self._m, self.Y, self.theta,
-    # self.indices, self.T, self.sigma, self.mode, self.eig_atol, self._prob
+    # subclasses provide: _lamN(), _warn_dl(), self._dev (BasicLanczos: a basis of basic_lanczos_recurrence's protocol,
+    # _LanczosDevice; IRAM: _BlockLanczosDevice -- .V, .ctx, .n, basis_to_host are what is used here), self._m, self.Y,
+    # self.theta, self.indices, self.T, self.sigma, self.mode, self.eig_atol, self._prob
+
+    def _open(self, A, B, factor, sigma, device_problem=True):
+        """every solve() starts here: operators and shift kept as the reference keeps them, the context, the pencil on
+        the device (not for a solve without an adjoint stage); returns (ctx, prob)"""
+        self.factor = aslinearoperator(factor)
+        self.B = aslinearoperator(B)
+        self.A = aslinearoperator(A)
+        self.sigma = sigma
+        ctx = self._ctx or (factor.ctx if isinstance(factor, SpLuOperator) else default_context())
+        self._prob = DeviceProblem(ctx, A, B, factor, self.mode) if device_problem else None
+        return ctx, self._prob
 
     @property
     def V(self):
@@ -833,7 +998,8 @@ class _AdjointAPI:
 
 
 class BasicLanczos(_AdjointAPI):
-    """Un-restarted shift-invert Lanczos with B-orthogonalisation (ref 1331-1650); real dtype."""
+    """Un-restarted shift-invert Lanczos with B-orthogonalisation (ref 1331-1650): basic_lanczos_recurrence on a real
+    or, for complex-step matrices, a dual-number device basis."""
 
     def __init__(self, N=10, m=60, tol=1e-14, Ntarget=None, eig_atol=1e-5, mode="normal", ortho_type="full",
                  ctx=None):
@@ -861,209 +1027,44 @@ class BasicLanczos(_AdjointAPI):
     def _warn_dl(self):
         pass
 
-    def _reduced(self, m):
-        """eigh of the leading m x m tridiagonal + sort (ref 1416-1439)"""
-        T = np.diag(self.alpha[:m]) + np.diag(self.beta[: m - 1], 1) + np.diag(self.beta[: m - 1], -1)
-        theta, Y = np.linalg.eigh(T)
-        lam, indices = ritz_to_eigs(theta, self.sigma, self.mode)
-        return theta, Y, T, lam, indices
-
-    @staticmethod
-    def _converged(beta_last, Yrow, N, tol):
-        """leading run of sorted Ritz pairs with |beta y_last| < tol (ref 1441-1451)"""
-        count = 0
-        for e in np.abs(beta_last * Yrow):
-            if e < tol:
-                count += 1
-            else:
-                break
-        return count >= N
-
     def solve(self, A, B, factor, sigma):
+        """Complex A or B: the reference's complex-step evaluation (ref 1453-1650 with complex A, B and a
+        complex SuperLU, examples/buckling.py:1014-1023) in dual numbers.  Eigenvalues, eigenvectors and coefficients
+        come back complex, imaginary part = step * forward derivative; forward evaluation only, as in the reference."""
         n = _check_shapes(A, B, factor)
-        if np.issubdtype(np.dtype(A.dtype), np.complexfloating) or np.issubdtype(np.dtype(B.dtype), np.complexfloating):
-            return self._solve_complex_step(A, B, factor, sigma, n)
-        self.factor = aslinearoperator(factor)
-        self.B = aslinearoperator(B)
-        self.A = aslinearoperator(A)
-        self.sigma = sigma
-        ctx = self._ctx or (factor.ctx if isinstance(factor, SpLuOperator) else default_context())
-        prob = DeviceProblem(ctx, A, B, factor, self.mode)
-        self._prob = prob
-        mm = self.m_max
-        dev = _LanczosDevice(prob, mm + 1)
+        dual = any(np.issubdtype(np.dtype(X.dtype), np.complexfloating) for X in (A, B))
+        if dual:
+            Br, Bi = _split_complex_step_B(B, factor)
+        ctx, prob = self._open(A, B, factor, sigma, device_problem=not dual)
+        nV = self.m_max + 1
+        dev = _DualLanczosDevice(ctx, Br, Bi, factor, n, nV) if dual else _LanczosDevice(prob, nV)
         self._dev = dev
-        self.alpha = np.zeros(mm)
-        self.beta = np.zeros(mm)
-
-        v0 = np.random.default_rng(12345).uniform(size=n, low=-1.0, high=1.0)  # ref 1514-1515
-        v = ctx.from_host(v0)
-        dev.normalize_into(v, 0)
-
         Nchk = self.N if self.Ntarget is None else self.Ntarget
-        self.m = mm
-        S = BS = None
-        for i in range(1, mm + 1):
-            dev.apply_op(i - 1, v)                                         # ref 1524
-            if i > 1:
-                v.assign_lincomb([(1.0, v), (-self.beta[i - 2], dev.V[i - 2])])  # ref 1526
-            if self.ortho_type == "full":
-                h = dev.orthogonalize(v, i)                                # ref 1529-1534
-                self.alpha[i - 1] = h[i - 1]
-            else:
-                j0 = max(0, i - 2)                                         # ref 1563: the two previous vectors
-                h1 = dev.BV.dot(v, ns=i - j0, j0=j0)
-                dev.V.axpy_into(v, h1, alpha=-1.0, j0=j0)
-                self.alpha[i - 1] = h1[-1, 0]
-                if S is not None and S.k > 0:                              # ref 1571-1574
-                    hs = BS.tdot(v)
-                    v.add_product(S, hs, alpha=-1.0, beta=1.0)
-            self.beta[i - 1] = dev.normalize_into(v, i)                    # ref 1537-1538
-            if i >= 2:
-                theta, Y, T, lam, indices = self._reduced(i)
-                Y0 = Y[:, indices]
-                if self._converged(self.beta[i - 1], Y0[i - 1, :], Nchk, self.tol):
-                    self.m = i
-                    break
-                if self.ortho_type == "selective":                         # ref 1596-1605
-                    errs = np.abs(self.beta[i - 1] * Y0[i - 1, :])
-                    conv = [j for j in range(i) if errs[j] < np.sqrt(self.tol)]
-                    if conv:
-                        S = ctx.empty(n, len(conv))
-                        dev.V.times_into(S, Y0[:, conv], ns=i)
-                        BS = prob.opB.apply(S)
-                    else:
-                        S = BS = None
-
-        self.theta, self.Y, self.T, self.lam, self.indices = self._reduced(self.m)
-        if self.Ntarget is not None:                                       # ref 1615-1625
-            self.N = self.Ntarget
-            while self.N < self.m and _is_close(self.lam[self.indices[self.N - 1]], self.lam[self.indices[self.N]],
-                                                self.eig_atol):
-                self.N += 1
-        elif _is_close(self.lam[self.indices[self.N - 1]], self.lam[self.indices[self.N]], self.eig_atol):
-            warnings.warn(f"BasicLanczos: Ritz values {self.N} and {self.N+1} are numerically repeated.")
+        self.alpha, self.beta, self.m = basic_lanczos_recurrence(dev, self.m_max, Nchk, self.tol, self.ortho_type, sigma,
+                                                                 self.mode)
+        self.theta, self.Y, self.T, self.lam, self.indices = reduced_problem(self.alpha, self.beta, self.m, sigma, self.mode)
+        self.N = wanted_pairs(self.lam, self.indices, self.m, self.N, self.Ntarget, self.eig_atol)
         sel = self.indices[: self.N]
         self.lam0 = self.lam[sel]
         self.Y0 = self.Y[:, sel]
         self.eig_res = np.abs(self.beta[-1] * self.Y0[-1, :])              # ref 1640-1645
         self.fail = bool(np.any(self.eig_res > self.tol))
-        dPhi = ctx.empty(n, self.N)
-        dev.V.times_into(dPhi, self.Y0, ns=self.m)                         # ref 1648
-        prob.set_phi(Phi_dev=dPhi)
-        self.Phi = dPhi.get()
+        Phi = dev.ritz_vectors(self.Y0, self.m)                            # ref 1648
+        if dual:
+            self.Phi = Phi                                                 # (host, complex: no adjoint stage follows)
+        else:
+            prob.set_phi(Phi_dev=Phi)
+            self.Phi = Phi.get()
+            # Ritz pairs beyond N that pass the solver's own test |beta y_last| < tol: deflated by the adjoint stage too
+            if self.tol > 0:
+                bounds = np.abs(self.beta[self.m - 1] * self.Y[self.m - 1, :])
+                self._set_extra_pairs(prob, dev, self.lam, bounds, None, None, self.m,
+                                      max(0, min(self.N // 4, 128 - self.N)), absolute_tol=self.tol)
         self._phi_token = self.Phi
-        # Ritz pairs beyond N that pass the solver's own test |beta y_last| < tol: deflated by the adjoint stage too
-        if self.tol > 0:
-            bounds = np.abs(self.beta[self.m - 1] * self.Y[self.m - 1, :])
-            self._set_extra_pairs(prob, dev, self.lam, bounds, None, None, self.m, max(0, min(self.N // 4, 128 - self.N)),
-                                  absolute_tol=self.tol)
         self._m = self.m
-        self._nV = self.m_max + 1
+        self._nV = nV
         self._V_host = None
         return self.lam0, self.Phi
-
-
-def _solve_complex_step(self, A, B, factor, sigma, n):
-    """
-    The reference's complex-step evaluation (ref 1453-1650 with complex A, B and a complex SuperLU,
-    examples/buckling.py:1014-1023): the same recurrence in dual-number arithmetic on the device.  Eigenvalues,
-    eigenvectors and Lanczos coefficients come back complex, imaginary part = step * forward derivative.  Forward
-    evaluation only, as in the reference (its adjoint stage is never run on complex data).
-    """
-    from scipy import sparse
-
-    if not (isinstance(factor, SpLuOperator) and factor.dual):
-        raise TypeError("the complex-step path needs an eigd_amd.SpLuOperator built on the complex shifted matrix")
-    if not sparse.issparse(B):
-        raise TypeError("the complex-step path needs B as a scipy sparse matrix")
-    Bc = sparse.csr_matrix(B).astype(np.complex128)
-    Bc.sort_indices()
-    Br = sparse.csr_matrix((Bc.data.real.copy(), Bc.indices, Bc.indptr), shape=Bc.shape)
-    Bi = sparse.csr_matrix((Bc.data.imag.copy(), Bc.indices, Bc.indptr), shape=Bc.shape)
-    self.factor, self.B, self.A, self.sigma = aslinearoperator(factor), aslinearoperator(B), aslinearoperator(A), sigma
-    ctx = self._ctx or factor.ctx
-    mm = self.m_max
-    dev = _DualLanczosDevice(ctx, Br, Bi, factor, n, mm + 1)
-    self._dev, self._prob = dev, None
-    self.alpha = np.zeros(mm, dtype=complex)
-    self.beta = np.zeros(mm, dtype=complex)
-
-    v0 = np.random.default_rng(12345).uniform(size=n, low=-1.0, high=1.0)  # ref 1514-1515
-    vr, vi = ctx.from_host(v0), ctx.zeros(n, 1)
-    dev.normalize_into(vr, vi, 0)
-
-    def reduced(m):  # ref 1416-1439 with the complex _eigh
-        T = np.diag(self.alpha[:m]) + np.diag(self.beta[: m - 1], 1) + np.diag(self.beta[: m - 1], -1)
-        theta, Y = complex_step_eigh(T)
-        lam, indices = ritz_to_eigs(theta, self.sigma, self.mode)
-        return theta, Y, T, lam, indices
-
-    Nchk = self.N if self.Ntarget is None else self.Ntarget
-    self.m = mm
-    Sr = Si = BSr = BSi = None
-    for i in range(1, mm + 1):
-        dev.apply_op(i - 1, vr, vi)                                        # ref 1524
-        if i > 1:
-            dev.axpy_basis(vr, vi, -self.beta[i - 2], i - 2)              # ref 1526
-        if self.ortho_type == "full":
-            h = dev.project_out(vr, vi, 0, i)                             # ref 1529-1534
-            self.alpha[i - 1] = h[i - 1]
-        else:
-            j0 = max(0, i - 2)                                             # ref 1563: the two previous vectors
-            h = dev.project_out(vr, vi, j0, i - j0)
-            self.alpha[i - 1] = h[-1]
-            if Sr is not None:                                             # ref 1571-1574
-                for _ in range(2):
-                    hr = BSr.tdot(vr)
-                    hi = BSr.tdot(vi) + BSi.tdot(vr)
-                    vi.add_product(Sr, hi, alpha=-1.0, beta=1.0)
-                    vi.add_product(Si, hr, alpha=-1.0, beta=1.0)
-                    vr.add_product(Sr, hr, alpha=-1.0, beta=1.0)
-        self.beta[i - 1] = dev.normalize_into(vr, vi, i)                   # ref 1537-1538
-        if i >= 2:
-            theta, Y, T, lam, indices = reduced(i)
-            Y0 = Y[:, indices]
-            if self._converged(self.beta[i - 1], Y0[i - 1, :], Nchk, self.tol):
-                self.m = i
-                break
-            if self.ortho_type == "selective":                             # ref 1596-1605
-                errs = np.abs(self.beta[i - 1] * Y0[i - 1, :])
-                conv = [j for j in range(i) if errs[j] < np.sqrt(self.tol)]
-                if conv:
-                    S = dev.times(Y0[:, conv], i)
-                    Sr, Si = ctx.from_host(np.ascontiguousarray(S.real)), ctx.from_host(np.ascontiguousarray(S.imag))
-                    BSr, BSi = ctx.empty(n, len(conv)), ctx.empty(n, len(conv))
-                    tmp = ctx.empty(n, len(conv))
-                    dev.Br.apply(Sr, BSr)
-                    dev.Br.apply(Si, BSi)
-                    dev.Bi.apply(Sr, tmp)
-                    BSi.assign_lincomb([(1.0, BSi), (1.0, tmp)])
-                else:
-                    Sr = Si = BSr = BSi = None
-
-    self.theta, self.Y, self.T, self.lam, self.indices = reduced(self.m)
-    if self.Ntarget is not None:                                           # ref 1615-1625
-        self.N = self.Ntarget
-        while self.N < self.m and _is_close(self.lam[self.indices[self.N - 1]].real, self.lam[self.indices[self.N]].real,
-                                            self.eig_atol):
-            self.N += 1
-    elif _is_close(self.lam[self.indices[self.N - 1]].real, self.lam[self.indices[self.N]].real, self.eig_atol):
-        warnings.warn(f"BasicLanczos: Ritz values {self.N} and {self.N+1} are numerically repeated.")
-    sel = self.indices[: self.N]
-    self.lam0 = self.lam[sel]
-    self.Y0 = self.Y[:, sel]
-    self.eig_res = np.abs(self.beta[-1] * self.Y0[-1, :])                  # ref 1640-1645
-    self.fail = bool(np.any(self.eig_res > self.tol))
-    self.Phi = dev.times(self.Y0, self.m)                                  # ref 1648
-    self._phi_token = self.Phi
-    self._m = self.m
-    self._nV = self.m_max + 1
-    self._V_host = None
-    return self.lam0, self.Phi
-
-
-BasicLanczos._solve_complex_step = _solve_complex_step
 
 
 class IRAM(_AdjointAPI):
@@ -1120,13 +1121,7 @@ class IRAM(_AdjointAPI):
         n = _check_shapes(A, B, factor)
         if np.issubdtype(np.dtype(A.dtype), np.complexfloating):
             raise TypeError("Input matrix is not real-valued.")
-        self.factor = aslinearoperator(factor)
-        self.B = aslinearoperator(B)
-        self.A = aslinearoperator(A)
-        self.sigma = sigma
-        ctx = self._ctx or (factor.ctx if isinstance(factor, SpLuOperator) else default_context())
-        prob = DeviceProblem(ctx, A, B, factor, self.mode)
-        self._prob = prob
+        ctx, prob = self._open(A, B, factor, sigma)
         m, k = self.m, self.N
         if not (k < m <= n):
             raise ValueError("ncv must be k<ncv<=n")  # scipy's message for the same condition

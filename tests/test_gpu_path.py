@@ -1104,6 +1104,36 @@ def test_g6_complex_step_point_on_the_device():
         eg.IRAM(N=6, mode="buckling").solve(G, K, fac, sigma)          # ARPACK is real only (scipy raises the same)
 
 
+def test_basic_lanczos_recurrence_on_the_device_bases_matches_the_host_stand_ins():
+    """one recurrence, four bases: twelve fully orthogonalised steps on the real (G4) and the complex-step (G6) pencil
+    through the device basis and through its numpy stand-in give the same Lanczos coefficients"""
+    import eigd_amd as eg
+    from eigd_amd.adjoint import DeviceProblem
+    from eigd_amd.lanczos import (_DualLanczosDevice, _LanczosDevice, _split_complex_step_B,
+                                  basic_lanczos_recurrence)
+    from test_basic_lanczos_host_cpu import dual_basis, real_basis
+    from test_oracle_golden import _complex_csr
+
+    mm = 12
+    g = load_golden("g4_laplace900_basiclanczos")
+    K, M, sigma = csr_from(g, "K"), csr_from(g, "M"), float(g["normal_sigma"])
+    fac = eg.SpLuOperator((K - sigma * M).tocsc())
+    dev = _LanczosDevice(DeviceProblem(fac.ctx, K, M, fac, "normal"), mm + 1)
+    runs = [(dev, real_basis(K, M, sigma, "normal", mm + 1), sigma, "normal", np.float64)]
+    g = load_golden("g6_buckling50_complexstep")
+    K, G, sigma = _complex_csr(g, "K"), _complex_csr(g, "G"), float(g["sigma"])
+    fac = eg.SpLuOperator((K + sigma * G).tocsc())
+    dev = _DualLanczosDevice(fac.ctx, *_split_complex_step_B(K, fac), fac, K.shape[0], mm + 1)
+    runs.append((dev, dual_basis(G, K, sigma, mm + 1), sigma, "buckling", np.complex128))
+    for dev, host, sigma, mode, dtype in runs:
+        ad, bd, md = basic_lanczos_recurrence(dev, mm, 6, 0.0, "full", sigma, mode)
+        ah, bh, mh = basic_lanczos_recurrence(host, mm, 6, 0.0, "full", sigma, mode)
+        assert md == mh == mm and ad.dtype == bd.dtype == dtype
+        scale = np.abs(ah).max()
+        print(f"{mode}: alpha {np.abs(ad - ah).max() / scale:.2e}, beta {np.abs(bd - bh).max() / scale:.2e} of max|alpha|")
+        assert np.abs(ad - ah).max() < 1e-8 * scale and np.abs(bd - bh).max() < 1e-8 * scale
+
+
 def test_c3_full_size_properties():
     """
     The benchmark configuration itself (BASELINE configs[2]: 706 x 706 Q4 column, 998 284 dof, 32 modes, IRAM m = 65),
